@@ -17,10 +17,15 @@ torch.distributed.run), every rank separates its own batch -- utterances are ind
 there is no data-path collective ("scaling": "weak").
 
 Prints ONE JSON line (rank 0): metric = real-time factor (audio seconds separated per wall
-second, whole job), plus frames/s, a roofline block for the dominant kernel (every leg of the step timed
-by itself with HIP events: the legs sum to <= the step), "extra_configs" -- the other BASELINE.json
-configurations and the batch-1 whole-utterance latency, a few graph replays each, AFTER the timed region --
-and the CPU baseline (oracle restatement on the host cores, N=1 only).
+second, whole job), plus frames/s and ms_per_step.  A plain run does only that: set up, warm up, time the K steps, print.
+
+    --full              adds, AFTER the timed region: a roofline block for the dominant kernel (every leg of the step timed
+                        by itself with HIP events: the legs sum to <= the step), the Lloyd passes and a second input set, the
+                        one-batch-at-a-time and resident-mask steps, "extra_configs" -- the other BASELINE.json configurations
+                        and the batch-1 whole-utterance latency, a few graph replays each --, the CPU baseline (oracle
+                        restatement on the host cores, N=1 only) and, at N > 1, the data-parallel training leg and per-rank health
+    --dump-outputs DIR  writes what the timed path returned in its last step as DIR/<name>.npy (inputs and weights are
+                        seeded: the same arguments give the same inputs, so two builds can be compared output for output)
 """
 import argparse
 import json
@@ -144,6 +149,24 @@ def time_replays(run, reps, warm=2):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
+
+
+def dump_outputs(outs, path, budget=60 << 20):
+    """``outs`` (name -> device tensor) as ``path/<name>.npy`` in float32 (float64 stays float64), at most ``budget`` bytes in all:
+    an array beyond its even share keeps a seeded sample of its flattened elements (sorted indices from a generator seeded with 0,
+    so the same shape samples the same elements in every run)."""
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(1, len(outs))
+    for name, t in outs.items():
+        flat = t.detach().reshape(-1)
+        flat = flat.double() if flat.dtype == torch.float64 else flat.float()
+        cap = share // flat.element_size()
+        if flat.numel() > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), cap))
+            arr = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        else:
+            arr = flat.cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(path, f"{name}.npy"), arr)
 
 
 def extra_configs(dev):
@@ -662,8 +685,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="dc_l2", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=0, help="override chunks per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs legs (other BASELINE configs, B = 1 latency, training step)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every secondary leg: roofline, Lloyd passes, "
+                    "second input set, other steps and configurations, CPU baseline, N > 1: data-parallel training and per-rank health")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed path's outputs of its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_configs legs (other BASELINE configs, B = 1 latency, "
+                    "training step) and, at N > 1, the data-parallel training leg")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--no-pipeline", action="store_true", help="deep clustering, 2 layers, <= 32 chunks: time the one-batch-at-a-time step instead "
                     "of the two-batch software pipeline (separation.DCPipeline)")
@@ -673,6 +700,8 @@ def main():
                     help="f32 = exact-fp32 MFMA; bf16x3 = split-bf16 (3 bf16 MFMAs per fp32 product, fp32 accumulate); "
                          "bf16 = opt-in plain bf16 products (fp32 accumulate), outside the 1e-4 parity contract")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     os.environ["ONSSEN_PRECISION"] = args.precision
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:      # plain `python bench.py --gpus N`: become the launcher
@@ -714,8 +743,14 @@ def main():
     SR, NFFT, HOP, T_FRAMES, N_SAMPLES = wl["SR"], wl["NFFT"], wl["HOP"], wl["T"], wl["N"]
     model, wav, wav_np, bin_masks, sd, step = wl["model"], wl["wav"], wl["wav_np"], wl["bin_masks"], wl["sd"], wl["step"]
 
+    last = {}
+
+    def step_kept():     # the captured call's outputs are the graph's own: every replay rewrites them
+        last["out"] = step()
+        return last["out"]
+
     with torch.no_grad():
-        run, graph = capture(step, not args.no_graph)
+        run, graph = capture(step_kept, not args.no_graph)
         # ---- the headline step as a STREAM of batches (round 6): deep clustering, two layers, <= 32 chunks run through the two-batch
         #      software pipeline -- replay k finishes batch k-1 (layer 1, fc_dc, 2-means, masks, iSTFT) and starts batch k (STFT, target
         #      map, layer 0, layer 1's projection), the two recurrences in ONE persistent launch on 16-row groups.  Every replay does the
@@ -763,11 +798,18 @@ def main():
             dist.all_reduce(te, op=dist.ReduceOp.MAX)
             elapsed = float(te.item())
 
+        if args.dump_outputs and rank == 0:       # before any later leg runs the step again
+            if pipe is not None:                  # the last replay finished batch k-1: its masks and separated waveforms
+                outs = {"masks": pipe.masks, "separated": pipe.out[(pipe.count - 1) & 1]}
+            else:
+                outs = dict(zip(("masks" if kind == "deep_clustering" else "embedding", "separated"), last["out"]))
+            dump_outputs(outs, args.dump_outputs)
+
         # ---- the clustering's work depends on the data: Lloyd passes the timed replays actually ran, and the SAME captured step
         #      on a SECOND set of B distinct utterances (other seeds), outside the timed region
         lloyd, second = None, None
         single = None
-        if kind == "deep_clustering" and rank == 0:
+        if args.full and kind == "deep_clustering" and rank == 0:
             def lloyd_now():       # the pipeline clusters batch k-1 in the workspace of the OTHER parity than the step it has just run
                 return lloyd_iterations(B, T_FRAMES, F, D, ws=pipe.cws[pipe.count & 1] if pipe is not None else None)
 
@@ -797,7 +839,7 @@ def main():
         # ---- the step of rounds 1-3 (binary masks resident in HBM instead of the clustering): a named secondary, outside
         #      the timed region, rank 0 only; captured and replayed like the headline
         dc_e2e = None
-        if kind == "deep_clustering" and rank == 0:
+        if args.full and kind == "deep_clustering" and rank == 0:
             run_rm, g_rm = capture(wl["step_resident_masks"], not args.no_graph)
             ms_rm = time_replays(run_rm, 10)
             dc_e2e = {"ms_per_step": ms_rm, "x_real_time": B * (T_FRAMES * HOP / SR) / ms_rm * 1e3,
@@ -807,7 +849,7 @@ def main():
 
         # ---- per-kernel timing leg (HIP events on the launch stream), outside the timed region
         roof = (kernel_roofline(model.chimera if kind == "phase_net" else model, wav, dev,
-                                "chimera" if kind == "phase_net" else kind, F, H, L, B, D, pipe=pipe) if rank == 0 else None)
+                                "chimera" if kind == "phase_net" else kind, F, H, L, B, D, pipe=pipe) if args.full and rank == 0 else None)
 
     ms_per_step = 1e3 * elapsed / args.steps
     frames = B * T_FRAMES * world * args.steps
@@ -882,7 +924,7 @@ def main():
     result["config"]["recurrence"] = ("XCD-local persistent kernel (one launch per layer)" if recurrence_plan(B, H)[1] & 4
                                       else "one launch per time step")
     result["config"]["xcd_placement_independent_protocol_used"] = _XcdStatus.safe_protocol_seen
-    if world > 1 and not args.no_extra:
+    if world > 1 and args.full and not args.no_extra:
         # ---- data-parallel training leg (the only path with a collective): every rank takes part.  The headline above is
         #      already final; a watchdog makes sure a wedged collective can only cost this leg, never the JSON line.
         import threading
@@ -903,7 +945,7 @@ def main():
             dp = {"error": f"rank {rank}: {type(e).__name__}: {e}"[:400]}
         dog.cancel()
         result["dp_training_step_dc_l3_b16"] = dp
-    if world > 1:
+    if world > 1 and args.full:
         # ---- per-rank health of the persistent kernels and the collective layer's settings IN FORCE (every rank reports; rank 0 prints):
         #      the first hardware N = 8 run must be able to tell "a rank fell back / aborted" from "RCCL got more channels than the two
         #      spare CUs per XCD hold" from the line alone
@@ -922,7 +964,8 @@ def main():
                                       "why": "one RCCL workgroup per channel; <= 16 channels = <= 2 workgroups per XCD = the CUs a 30-member "
                                              "recurrence group leaves free (onssen_amd/dist.py: configure_rccl)"}
     if rank == 0:
-        result["roofline"] = roof
+        if args.full:
+            result["roofline"] = roof
         if dc_e2e is not None:
             result["resident_mask_step"] = dc_e2e
         if lloyd is not None:
@@ -933,9 +976,9 @@ def main():
             result["one_batch_at_a_time_step"] = single
         from onssen_amd import options as _opt
         result["config"]["non_default_options"] = {k: v["value"] for k, v in _opt.describe().items() if v["value"] != v["default"] and k != "world_size"}
-        if world == 1 and not args.no_extra and args.config == "dc_l2" and args.precision == "bf16x3":
+        if args.full and world == 1 and not args.no_extra and args.config == "dc_l2" and args.precision == "bf16x3":
             result["extra_configs"] = extra_configs(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(sd, kind, wav_np, bin_masks.cpu().numpy())
         print(json.dumps(result), flush=True)
     if world > 1:

@@ -6,6 +6,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -74,7 +77,8 @@ def test_recorded_eight_rank_self_test_line():
 
 
 def test_recorded_bench_line_carries_the_contract():
-    """profiles/r06c_bench_final.json = `python3 bench.py --gpus 1 --steps 20 --warmup 5` on the GPU box (the driver's command): every
+    """profiles/r06c_bench_final.json = `python3 bench.py --gpus 1 --steps 20 --warmup 5` on the GPU box (the driver's command; the
+    secondary legs it carries now need `--full`, a plain run prints the headline keys only): every
     key the bench contract names, the roofline and CPU-baseline blocks (round 6: BASELINE.md section 3's protocol), the round-5 additions and
     (round 6b) the two-batch pipeline the headline step runs through, with the one-batch-at-a-time step beside it."""
     r = json.loads(open(os.path.join(ROOT, "profiles", "r06c_bench_final.json")).read().strip().splitlines()[-1])
@@ -129,3 +133,38 @@ def test_recorded_bench_line_carries_the_contract():
         assert rg["plain_call_on_2K_rows"][order]["x_real_time"] > 0
     assert rg["pipelined"]["as_they_come"]["x_real_time"] > rg["x_real_time"]
     assert rg["pipelined"]["bucketed_by_length"]["x_real_time"] > rg["bucketed_by_length"]["x_real_time"]
+
+
+def test_dump_outputs_keeps_small_arrays_and_samples_large_ones_the_same_way_every_time(tmp_path):
+    """--dump-outputs: an array within its share of the budget is written whole, in its shape; a larger one as a seeded sample of
+    its elements, the same sample in every run, so that two builds' dumps compare element for element."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import torch
+    g = torch.Generator().manual_seed(0)
+    outs = {"masks": torch.rand(4, 10, 9, 2, generator=g), "embedding": torch.randn(50_000, generator=g, dtype=torch.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / d), budget=200_000)
+    m = np.load(tmp_path / "a" / "masks.npy")
+    assert m.dtype == np.float32 and m.shape == (4, 10, 9, 2) and np.array_equal(m, outs["masks"].numpy())
+    e = np.load(tmp_path / "a" / "embedding.npy")
+    assert e.dtype == np.float64 and 0 < e.size <= 100_000 // 8 and np.isin(e, outs["embedding"].numpy()).all()
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in ("masks.npy", "embedding.npy")) <= 200_000 + 2 * 256   # + .npy headers
+    for f in ("masks.npy", "embedding.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_last_step(tmp_path):
+    """A plain run prints the headline keys only (the secondary legs need --full), times exactly --steps steps, and writes the
+    pipelined step's outputs: the binary masks and the two separated waveforms of a 32-chunk batch."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--preheat", "0",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["metric"] == "real_time_factor"
+    assert abs(line["value"] - 32 * 3.2 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert not {"roofline", "cpu_baseline", "extra_configs", "second_input_set"} & set(line)
+    masks, sep = np.load(tmp_path / "masks.npy"), np.load(tmp_path / "separated.npy")
+    assert masks.shape == (32, 400, 129, 2) and sep.shape == (32, 2, 25536) and masks.dtype == sep.dtype == np.float32
+    assert set(np.unique(masks)) <= {0.0, 1.0} and np.isfinite(sep).all() and np.abs(sep).max() > 0

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Same-box A/B of an environment switch: python tools/ab_env.py VAR v1 v2 ... -- bench.py args...  (every value twice, interleaved)."""
+"""Same-box A/B of an environment switch: python tools/ab_env.py VAR v1 v2 ... -- bench.py --full args...  (every value twice, interleaved;
+--full: the GEMM legs and the one-batch-at-a-time step it prints are secondary legs of the bench line)."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 i = sys.argv.index("--")

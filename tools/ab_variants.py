@@ -5,7 +5,7 @@ headline step on two boxes), so a comparison is only worth anything when both bi
   build (here, no GPU):   python tools/ab_variants.py build base "" poll0 "-DONSSEN_SOME_SWITCH=1" ...
                           -> build_variants/libonssen_hip_<name>.so, one per (name, extra hipcc flags) pair; a variant can
                              also be produced by hand (git stash / build / copy) under the same file name
-  run (on the GPU box):   gpurun -- 'python tools/ab_variants.py run base poll0 -- bench.py --no-cpu-baseline --steps 40'
+  run (on the GPU box):   python tools/ab_variants.py run base poll0 -- bench.py --full --no-cpu-baseline --steps 40
                           -> every variant twice, interleaved, printing ms_per_step and the recurrence us per time step;
                              the in-tree library is restored afterwards
 build_variants/ is git-ignored but travels to the GPU box with the snapshot."""

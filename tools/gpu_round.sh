@@ -14,13 +14,13 @@ except Exception as e:
     print("$name FAILED", e, open("gpurun_out/bench_$name.err").read()[-400:])
 PY
 }
-BENCH_ARGS="" run dc_l2_bf16x3 A=1
-BENCH_ARGS="--config dc_l2 --precision f32 --no-cpu-baseline --no-extra" run dc_l2_f32 A=1
-BENCH_ARGS="--config dc_l2 --no-cpu-baseline --no-extra" run dc_l2_bf16x3_steps ONSSEN_XCD=0
-BENCH_ARGS="--config dc_l3 --no-cpu-baseline --no-extra" run dc_l3 A=1
-BENCH_ARGS="--config chimera_l4 --no-cpu-baseline --no-extra" run chimera_l4 A=1
-BENCH_ARGS="--config phase_l4 --no-cpu-baseline --no-extra" run phase_l4 A=1
-BENCH_ARGS="--config dc_l2 --precision bf16 --no-cpu-baseline --no-extra" run dc_l2_bf16_optin A=1
+BENCH_ARGS="--full" run dc_l2_bf16x3 A=1
+BENCH_ARGS="--full --config dc_l2 --precision f32 --no-cpu-baseline --no-extra" run dc_l2_f32 A=1
+BENCH_ARGS="--full --config dc_l2 --no-cpu-baseline --no-extra" run dc_l2_bf16x3_steps ONSSEN_XCD=0
+BENCH_ARGS="--full --config dc_l3 --no-cpu-baseline --no-extra" run dc_l3 A=1
+BENCH_ARGS="--full --config chimera_l4 --no-cpu-baseline --no-extra" run chimera_l4 A=1
+BENCH_ARGS="--full --config phase_l4 --no-cpu-baseline --no-extra" run phase_l4 A=1
+BENCH_ARGS="--full --config dc_l2 --precision bf16 --no-cpu-baseline --no-extra" run dc_l2_bf16_optin A=1
 for cfg in "1 3" "0 3" "1 2"; do
   set -- $cfg; mode=$1; layers=$2
   ONSSEN_TRAIN_HIP=$mode timeout 300 python tools/train_step_bench.py --layers $layers --steps 10 --warmup 3 2> gpurun_out/train_${mode}_l$layers.err < /dev/null | tail -1 > gpurun_out/train_hip${mode}_l$layers.json

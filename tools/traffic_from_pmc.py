@@ -19,7 +19,7 @@ def mean(name_part, counter, exclude=None):
     return (sum(v) / len(v), len(v)) if v else (None, 0)
 
 
-out = {"round": tag, "source": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over bench.py --steps 1 --warmup 1 "
+out = {"round": tag, "source": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over bench.py --full --steps 1 --warmup 1 "
                                f"--no-graph (dc_l2, 32 x 400 frames); tools/profile_round.sh {tag}"}
 # the plain stacked instantiation (FUSE = false, TERMS = 3, STACK = true): layer 1 of the headline step
 kname = "lstm_xcd_kernel<5, 8, false, 3, true"
