@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ONSSEN_ABI_VERSION 14   /* 14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
+#define ONSSEN_ABI_VERSION 14   /* 14 (additions, no signature changed): onssen_tasnet_* (the Conv-TasNet separation forward).  14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
 
 #define ONSSEN_OK 0
 #define ONSSEN_E_ARG (-1)         /* invalid argument / unsupported shape */
@@ -687,6 +687,45 @@ int onssen_debug_cotenant_spin(int workgroups, int threads, long long ticks, int
  * up at once -- abort-path tests; data-parallel training raises it, see onssen_amd/dist.py), new_limit < 0 only queries.
  * Returns the previous value.  Process-wide; takes effect at the next launch. */
 long long onssen_xcd_spin_limit(long long new_limit);
+
+/* ---------------------------------------------------------------------------------------------
+ * Conv-TasNet separation forward (onssen/nn/tasnet.py:166-264), eval semantics.
+ * cfg_host: 12 HOST int32 values {N, L, B, H, P, X, R, norm, num_spks, activate, causal, precision}; norm / activate /
+ *   precision take the ONSSEN_TASNET_* values below.  Limits: L even, 2 <= L <= 64, N <= 1024, P <= 32 (odd unless causal),
+ *   X <= 30, num_spks <= 8.
+ * params: the flat fp32 parameters (device), in this order: encoder.weight [N][L], encoder.bias [N], LayerN_S.weight [N],
+ *   LayerN_S.bias [N], BottleN_S.weight [B][N], BottleN_S.bias [B]; for each block r * X + x: conv1x1.weight [H][B],
+ *   conv1x1.bias [H], PReLU_1.weight [1], norm_1 (gln / cln: weight [H], bias [H]; bn: weight, bias, running_mean,
+ *   running_var [H] each), dwconv.weight [H][P], dwconv.bias [H], Sc_conv.weight [B][H], Sc_conv.bias [B]; then
+ *   gen_masks.weight [num_spks N][B], gen_masks.bias [num_spks N], decoder.weight [N][L], decoder.bias [1]
+ *   (onssen_tasnet_param_floats values).  PReLU_2 / norm_2 are not used by the reference's forward and are not passed.
+ * image: onssen_tasnet_image_bytes() bytes, 256-byte aligned, written by onssen_tasnet_pack_f32 (stream-ordered); one image
+ *   serves every precision.
+ * forward: x (n, S) with row stride x_stride >= S floats; T = (S - L) / (L/2) + 1 frames, S_out = (T - 1) L/2 + L;
+ *   out = num_spks x n x S_out (contiguous); ws = onssen_tasnet_workspace_bytes(cfg, n, S) bytes, 256-byte aligned, no
+ *   zeroing needed.  The 1x1 convolutions run on onssen_linear_f32 (precision F32) or an x3 image + onssen_linear_x3p
+ *   (BF16X3, BF16).  Deterministic: no atomics; gLN statistics are fp64 partial sums merged in a fixed order.
+ */
+#define ONSSEN_TASNET_GLN 0
+#define ONSSEN_TASNET_CLN 1
+#define ONSSEN_TASNET_BN 2
+#define ONSSEN_TASNET_RELU 0
+#define ONSSEN_TASNET_SIGMOID 1
+#define ONSSEN_TASNET_SOFTMAX 2
+#define ONSSEN_TASNET_F32 0
+#define ONSSEN_TASNET_BF16X3 1
+#define ONSSEN_TASNET_BF16 2
+/* OR-ed into precision, shifted left by 8: these 1x1 convolutions run on exact fp32 whatever the precision */
+#define ONSSEN_TASNET_EXACT_BOTTLENECK 1
+#define ONSSEN_TASNET_EXACT_CONV1X1 2
+#define ONSSEN_TASNET_EXACT_SC_CONV 4
+#define ONSSEN_TASNET_EXACT_MASKS 8
+int64_t onssen_tasnet_param_floats(const int32_t* cfg_host);
+size_t onssen_tasnet_image_bytes(const int32_t* cfg_host);
+int onssen_tasnet_pack_f32(const int32_t* cfg_host, const float* params, void* image, size_t image_bytes, void* stream);
+size_t onssen_tasnet_workspace_bytes(const int32_t* cfg_host, int n, int S);
+int onssen_tasnet_forward_f32(const int32_t* cfg_host, const void* image, const float* x, int n, int S, int64_t x_stride,
+                              float* out, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,10 @@ BLSTM_G_READY = 128
 BLSTM_WS_DIRTY = 65536
 LSTM_BWD_STEPS, LSTM_BWD_XCD = 0, 1
 DC_CLUSTER_LAUNCH_PER_ITERATION = 1
-BLSTM_WS_HEADER = 32768   # ONSSEN_BLSTM_WS_HEADER_BYTES: zeroed once by the workspace owner
+BLSTM_WS_HEADER = 32768
+TASNET_GLN, TASNET_CLN, TASNET_BN = 0, 1, 2
+TASNET_RELU, TASNET_SIGMOID, TASNET_SOFTMAX = 0, 1, 2
+TASNET_F32, TASNET_BF16X3, TASNET_BF16 = 0, 1, 2   # ONSSEN_BLSTM_WS_HEADER_BYTES: zeroed once by the workspace owner
 
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 _pp = C.POINTER(C.c_void_p)
@@ -120,6 +123,11 @@ SIGNATURES = {
     "onssen_dc_cluster_ragged_f32": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _i, _f, _vp, _vp, _sz, _i, _vp]),
     "onssen_mask_istft_ragged_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "onssen_batch_sdr_ragged_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "onssen_tasnet_param_floats": (_i64, [_vp]),
+    "onssen_tasnet_image_bytes": (_sz, [_vp]),
+    "onssen_tasnet_pack_f32": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "onssen_tasnet_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "onssen_tasnet_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -160,6 +168,37 @@ class Lib:
 
     def lstm_pack_wih_bf16x3(self, w_ih, in_dim, H, ug, out, stream):
         self.check(self.dll.onssen_lstm_pack_wih_bf16x3(w_ih, in_dim, H, ug, out, stream), "onssen_lstm_pack_wih_bf16x3")
+
+    # ---- Conv-TasNet forward ------------------------------------------
+    @staticmethod
+    def tasnet_cfg(N, L, B, H, P, X, R, norm, spk, act, causal, prec):
+        """The 12 host int32 values of a Conv-TasNet configuration (include/onssen_hip.h); keep the object alive across calls."""
+        return (C.c_int32 * 12)(N, L, B, H, P, X, R, norm, spk, act, int(bool(causal)), prec)
+
+    def tasnet_param_floats(self, cfg):
+        n = int(self.dll.onssen_tasnet_param_floats(cfg))
+        if n < 0:
+            self.check(n, "onssen_tasnet_param_floats")
+        return n
+
+    def tasnet_image_bytes(self, cfg):
+        n = int(self.dll.onssen_tasnet_image_bytes(cfg))
+        if n == 0:
+            self.check(-1, "onssen_tasnet_image_bytes")
+        return n
+
+    def tasnet_pack(self, cfg, params, image, image_bytes, stream):
+        self.check(self.dll.onssen_tasnet_pack_f32(cfg, params, image, image_bytes, stream), "onssen_tasnet_pack_f32")
+
+    def tasnet_workspace_bytes(self, cfg, n, S):
+        nb = int(self.dll.onssen_tasnet_workspace_bytes(cfg, n, S))
+        if nb == 0:
+            self.check(-1, "onssen_tasnet_workspace_bytes")
+        return nb
+
+    def tasnet_forward(self, cfg, image, x, n, S, x_stride, out, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_tasnet_forward_f32(cfg, image, x, n, S, x_stride, out, ws, ws_bytes, stream),
+                   "onssen_tasnet_forward_f32")
 
     # ---- host-side wav reader (no device work) ---------------------------
     def wav_info(self, path):

@@ -1,0 +1,478 @@
+// Conv-TasNet separation forward (onssen/nn/tasnet.py:166-264), eval semantics.
+//
+// Layout: activations are time-major rows, row = b * T + t (b = utterance, t = encoder frame), the channels of a row
+// contiguous -- every 1x1 convolution is then a row GEMM Y = X W^T + b over the existing GEMM family (onssen_linear_f32 for
+// exact fp32, an x3 image + onssen_linear_x3p for split-bf16 / bf16).  The kernels here do what lies between the GEMMs:
+//   tas_encoder_kernel      Conv1d(1, N, L, stride L/2) + LayerN_S (LayerNorm over the N channels of each frame)
+//   tas_prelu_stats_kernel  PReLU_1 in place + the statistics of norm_1: gLN partial sums per (utterance, 64-frame chunk) in
+//                           fp64, cLN mean / rstd per row; BatchNorm needs none (running statistics)
+//   tas_dwconv_kernel       gLN partials reduced in a fixed order, norm_1 applied on load (a per-channel affine), the dilated
+//                           depthwise convolution with zero padding on the NORMALISED signal (causal: left padding only)
+//   tas_residual_kernel     x += Sc_conv(...)
+//   tas_mask_kernel         mask activation (relu / sigmoid / softmax across speakers) times the encoder output w, in place
+//   tas_decoder_kernel      ConvTranspose1d(N, 1, L, stride L/2): per frame a contraction over N, then the overlap-add of the
+//                           two frames that cover each output sample, plus the bias; each output sample has exactly one owner
+// No atomics, no spinning, no allocation: the whole forward is a fixed sequence of ordinary launches on one stream.
+// PReLU_2 / norm_2 exist upstream but the block's forward never calls them (tasnet.py:149-163): they are not packed.
+
+namespace tas {
+
+constexpr int ROWS_PER_CHUNK = 64;      // gLN partial sums: one per (utterance, 64 frames)
+constexpr int DW_ROWS = 32;             // depthwise convolution: frames per workgroup
+constexpr int DEC_FRAMES = 16;          // decoder: 16 hop-sized output blocks per workgroup
+constexpr int MAX_L = 64, MAX_N = 1024, MAX_SPK = 8, MAX_P = 32;
+constexpr float EPS = 1e-5f;            // GlobalLayerNorm, LayerNorm and BatchNorm1d defaults of the reference
+
+struct Cfg {
+  int N, L, B, H, P, X, R, norm, spk, act, causal, prec, exact;   // exact: ONSSEN_TASNET_EXACT_* kinds kept on exact fp32
+};
+
+static bool read_cfg(const int32_t* c, Cfg* g) {
+  if (!c) return false;
+  *g = Cfg{c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10], c[11] & 0xff, (c[11] >> 8) & 0xff};
+  if (g->N <= 0 || g->N > MAX_N || g->L < 2 || g->L > MAX_L || (g->L % 2) != 0) return false;
+  if (g->B <= 0 || g->H <= 0 || g->P <= 0 || g->P > MAX_P || g->X <= 0 || g->R <= 0 || g->X > 30) return false;
+  if (!g->causal && (g->P % 2) == 0) return false;                 // non-causal even P changes the frame count upstream
+  if (g->norm < ONSSEN_TASNET_GLN || g->norm > ONSSEN_TASNET_BN) return false;
+  if (g->spk <= 0 || g->spk > MAX_SPK) return false;
+  if (g->act < ONSSEN_TASNET_RELU || g->act > ONSSEN_TASNET_SOFTMAX) return false;
+  if (g->prec < ONSSEN_TASNET_F32 || g->prec > ONSSEN_TASNET_BF16 || (c[11] >> 16) != 0 || g->exact > 15) return false;
+  return true;
+}
+
+static inline size_t al(size_t x) { return align256(x); }
+static inline int ld4(int k) { return (k + 3) / 4 * 4; }
+
+// Offsets (bytes) of the weight image: fp32 copies (1x1 weights padded to a multiple of 4 columns, zeros beyond K) followed by
+// the x3 images of the four GEMM weight kinds.  The image does not depend on the precision: one image serves all three.
+struct Layout {
+  size_t enc_w, enc_b, ln_g, ln_b, bott_w, bott_b, mask_w, mask_b, dec_w, dec_b, blk0, blk_stride;
+  size_t c1_w, c1_b, alpha, n_a, n_b, dw_w, dw_b, sc_w, sc_b;     // inside a block
+  size_t bott_x3, mask_x3, x3_blk0, x3_blk_stride, c1_x3, sc_x3, total;
+};
+
+static Layout layout(const Cfg& g) {
+  Layout o;
+  const int ldN = ld4(g.N), ldB = ld4(g.B), ldH = ld4(g.H);
+  size_t p = 0;
+  auto take = [&](size_t floats) { const size_t at = p; p += al(floats * 4); return at; };
+  o.enc_w = take((size_t)g.N * g.L); o.enc_b = take(g.N); o.ln_g = take(g.N); o.ln_b = take(g.N);
+  o.bott_w = take((size_t)g.B * ldN); o.bott_b = take(g.B);
+  o.mask_w = take((size_t)g.spk * g.N * ldB); o.mask_b = take((size_t)g.spk * g.N);
+  o.dec_w = take((size_t)g.N * g.L); o.dec_b = take(1);
+  o.blk0 = p;
+  size_t q = 0;
+  auto tb = [&](size_t floats) { const size_t at = q; q += al(floats * 4); return at; };
+  o.c1_w = tb((size_t)g.H * ldB); o.c1_b = tb(g.H); o.alpha = tb(1); o.n_a = tb(g.H); o.n_b = tb(g.H);
+  o.dw_w = tb((size_t)g.H * g.P); o.dw_b = tb(g.H); o.sc_w = tb((size_t)g.B * ldH); o.sc_b = tb(g.B);
+  o.blk_stride = q;
+  p += q * (size_t)(g.R * g.X);
+  const int kbN = ceil_div(g.N, 32), kbB = ceil_div(g.B, 32), kbH = ceil_div(g.H, 32);
+  o.bott_x3 = p; p += al((size_t)g.B * kbN * 128);
+  o.mask_x3 = p; p += al((size_t)g.spk * g.N * kbB * 128);
+  o.x3_blk0 = p;
+  o.c1_x3 = 0; o.sc_x3 = al((size_t)g.H * kbB * 128);
+  o.x3_blk_stride = o.sc_x3 + al((size_t)g.B * kbH * 128);
+  p += o.x3_blk_stride * (size_t)(g.R * g.X);
+  o.total = p;
+  return o;
+}
+
+// floats of the flat parameter buffer onssen_tasnet_pack_f32 reads (see include/onssen_hip.h for the order)
+static int64_t param_floats(const Cfg& g) {
+  const int64_t nb = g.norm == ONSSEN_TASNET_BN ? 4 : 2;
+  const int64_t blk = (int64_t)g.H * g.B + g.H + 1 + nb * g.H + (int64_t)g.H * g.P + g.H + (int64_t)g.B * g.H + g.B;
+  return (int64_t)g.N * g.L + 3LL * g.N + (int64_t)g.B * g.N + g.B + blk * g.R * g.X + (int64_t)g.spk * g.N * g.B +
+         (int64_t)g.spk * g.N + (int64_t)g.N * g.L + 1;
+}
+
+// Workspace (bytes, each region 256-aligned): w [M][N], e / depthwise output [M][max(N, H)], x [M][B], c [M][H],
+// t [M][max(B, spk N)], the GEMM A-operand image [M][KBmax][2][32], statistics (max of gLN partials and cLN rows).
+struct Ws {
+  size_t w, e, x, c, t, img, st, total;
+};
+
+static Ws ws_layout(const Cfg& g, int n, int S) {
+  Ws o;
+  const int T = (S - g.L) / (g.L / 2) + 1;
+  const size_t M = (size_t)n * T;
+  const int kbmax = ceil_div(g.N > g.B ? (g.N > g.H ? g.N : g.H) : (g.B > g.H ? g.B : g.H), 32);
+  const int NH = g.N > g.H ? g.N : g.H, BS = g.B > g.spk * g.N ? g.B : g.spk * g.N;
+  const size_t nch = (size_t)ceil_div(T, ROWS_PER_CHUNK);
+  const size_t st_bytes = (size_t)n * nch * 2 * sizeof(double) > M * 2 * sizeof(float) ? (size_t)n * nch * 2 * sizeof(double)
+                                                                                      : M * 2 * sizeof(float);
+  size_t p = 0;
+  o.w = p; p += al(M * g.N * 4);
+  o.e = p; p += al(M * NH * 4);
+  o.x = p; p += al(M * g.B * 4);
+  o.c = p; p += al(M * g.H * 4);
+  o.t = p; p += al(M * BS * 4);
+  o.img = p; p += al(M * kbmax * 128);
+  o.st = p; p += al(st_bytes);
+  o.total = p;
+  return o;
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+// ---- packing ----------------------------------------------------------------------------------------------------------------
+// rows x K (row-major, contiguous) -> rows x ld (zeros in columns [K, ld))
+__global__ __launch_bounds__(256) void tas_copy_pad_kernel(const float* __restrict__ src, long rows, int K, int ld,
+                                                           float* __restrict__ dst) {
+  const long total = rows * ld;
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    const long r = e / ld;
+    const int k = (int)(e % ld);
+    dst[e] = k < K ? src[r * K + k] : 0.0f;
+  }
+}
+
+// BatchNorm1d (eval) folded to a per-channel affine: a = g / sqrt(var + eps), b = beta - mean a (fp64)
+__global__ __launch_bounds__(256) void tas_fold_bn_kernel(const float* __restrict__ g, const float* __restrict__ be,
+                                                          const float* __restrict__ mu, const float* __restrict__ var, int H,
+                                                          float* __restrict__ a, float* __restrict__ b) {
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < H; c += gridDim.x * blockDim.x) {
+    const double s = (double)g[c] / sqrt((double)var[c] + (double)EPS);
+    a[c] = (float)s;
+    b[c] = (float)((double)be[c] - (double)mu[c] * s);
+  }
+}
+
+// ---- K1: encoder + LayerN_S -------------------------------------------------------------------------------------------------
+// One wave per frame; lane j owns channels j, j + 64, ... (N <= 1024: 16 per lane, register-resident).
+__global__ __launch_bounds__(256) void tas_encoder_kernel(const float* __restrict__ x, long x_s, int T, long M, int N, int L,
+                                                          const float* __restrict__ ew, const float* __restrict__ eb,
+                                                          const float* __restrict__ g, const float* __restrict__ be,
+                                                          float* __restrict__ w_out, float* __restrict__ e_out) {
+  const int ln = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;                               // no barrier in this kernel
+  const long b = row / T;
+  const int t = (int)(row % T);
+  const float* fr = x + b * x_s + (long)t * (L / 2);
+  float v[MAX_N / 64];
+  float s = 0.0f;
+#pragma unroll
+  for (int i = 0; i < MAX_N / 64; ++i) {
+    const int c = ln + 64 * i;
+    float acc = 0.0f;
+    if (c < N) {
+      acc = eb[c];
+      for (int l = 0; l < L; ++l) acc += ew[c * L + l] * fr[l];
+      w_out[row * N + c] = acc;
+      s += acc;
+    }
+    v[i] = acc;
+  }
+  const float mean = wave_sum(s) / (float)N;
+  float q = 0.0f;
+#pragma unroll
+  for (int i = 0; i < MAX_N / 64; ++i)
+    if (ln + 64 * i < N) q += (v[i] - mean) * (v[i] - mean);
+  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)N + EPS);
+#pragma unroll
+  for (int i = 0; i < MAX_N / 64; ++i) {
+    const int c = ln + 64 * i;
+    if (c < N) e_out[row * N + c] = (v[i] - mean) * rstd * g[c] + be[c];
+  }
+}
+
+// ---- PReLU_1 + statistics of norm_1 -----------------------------------------------------------------------------------------
+// grid (chunks of 64 frames, utterances); each wave takes every 4th frame of the chunk.
+//   gLN: fp64 (sum, sum of squares) of the chunk -> part[(b * nch + chunk) * 2 + {0, 1}] (fixed order: lanes, then waves)
+//   cLN: per frame (mean, rstd) -> rstat[row * 2 + {0, 1}] (two passes over the row, as LayerNorm)
+__global__ __launch_bounds__(256) void tas_prelu_stats_kernel(float* __restrict__ c, int T, int H, const float* __restrict__ alpha,
+                                                              int norm, double* __restrict__ part, float* __restrict__ rstat) {
+  __shared__ double red[4][2];
+  const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b = blockIdx.y, nch = gridDim.x;
+  const int t0 = blockIdx.x * ROWS_PER_CHUNK, t1 = t0 + ROWS_PER_CHUNK < T ? t0 + ROWS_PER_CHUNK : T;
+  const float a = alpha[0];
+  double s = 0.0, q = 0.0;
+  for (int t = t0 + wv; t < t1; t += 4) {
+    float* r = c + ((long)b * T + t) * H;
+    float rs = 0.0f;
+    for (int k = ln; k < H; k += 64) {
+      float v = r[k];
+      v = v >= 0.0f ? v : a * v;
+      r[k] = v;
+      if (norm == ONSSEN_TASNET_GLN) { s += (double)v; q += (double)v * (double)v; }
+      rs += v;
+    }
+    if (norm == ONSSEN_TASNET_CLN) {
+      const float mean = wave_sum(rs) / (float)H;
+      float rq = 0.0f;
+      for (int k = ln; k < H; k += 64) rq += (r[k] - mean) * (r[k] - mean);
+      const float var = wave_sum(rq) / (float)H;
+      if (ln == 0) {
+        rstat[((long)b * T + t) * 2] = mean;
+        rstat[((long)b * T + t) * 2 + 1] = 1.0f / sqrtf(var + EPS);
+      }
+    }
+  }
+  if (norm == ONSSEN_TASNET_GLN) {
+    s = wave_sum_d(s);
+    q = wave_sum_d(q);
+    if (ln == 0) { red[wv][0] = s; red[wv][1] = q; }
+  }
+  __syncthreads();
+  if (norm == ONSSEN_TASNET_GLN && threadIdx.x == 0) {
+    part[((long)b * nch + blockIdx.x) * 2] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+    part[((long)b * nch + blockIdx.x) * 2 + 1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+  }
+}
+
+// ---- K2: norm_1 on load + dilated depthwise convolution ----------------------------------------------------------------------
+// grid (chunks of 32 frames, utterances); threads over channels.  Output frame t reads normalised frames t + d p - pad_l,
+// zeros outside [0, T).
+__global__ __launch_bounds__(256) void tas_dwconv_kernel(const float* __restrict__ c, int T, int H, int P, int dil, int pad_l,
+                                                         int norm, const double* __restrict__ part, int nch,
+                                                         const float* __restrict__ rstat, const float* __restrict__ na,
+                                                         const float* __restrict__ nb, const float* __restrict__ dw,
+                                                         const float* __restrict__ dwb, float* __restrict__ out) {
+  __shared__ float gstat[2];
+  const int b = blockIdx.y;
+  if (threadIdx.x == 0) {
+    float mean = 0.0f, rstd = 1.0f;
+    if (norm == ONSSEN_TASNET_GLN) {
+      double s = 0.0, q = 0.0;
+      for (int i = 0; i < nch; ++i) { s += part[((long)b * nch + i) * 2]; q += part[((long)b * nch + i) * 2 + 1]; }
+      const double cnt = (double)T * H, m = s / cnt;
+      double var = q / cnt - m * m;
+      var = var > 0.0 ? var : 0.0;
+      mean = (float)m;
+      rstd = (float)(1.0 / sqrt(var + (double)EPS));
+    }
+    gstat[0] = mean;
+    gstat[1] = rstd;
+  }
+  __syncthreads();
+  const float gmean = gstat[0], grstd = gstat[1];
+  const int t0 = blockIdx.x * DW_ROWS, t1 = t0 + DW_ROWS < T ? t0 + DW_ROWS : T;
+  const long base = (long)b * T;
+  for (int k = threadIdx.x; k < H; k += blockDim.x) {
+    const float ga = na[k], gb = nb[k], bias = dwb[k];
+    for (int t = t0; t < t1; ++t) {
+      float acc = bias;
+      for (int p = 0; p < P; ++p) {
+        const int tau = t + dil * p - pad_l;
+        if (tau < 0 || tau >= T) continue;
+        const float v = c[(base + tau) * H + k];
+        float nv;
+        if (norm == ONSSEN_TASNET_GLN) nv = (v - gmean) * grstd * ga + gb;
+        else if (norm == ONSSEN_TASNET_CLN) nv = (v - rstat[(base + tau) * 2]) * rstat[(base + tau) * 2 + 1] * ga + gb;
+        else nv = v * ga + gb;
+        acc += dw[k * P + p] * nv;
+      }
+      out[(base + t) * H + k] = acc;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void tas_residual_kernel(float* __restrict__ x, const float* __restrict__ y, long n) {
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) x[e] += y[e];
+}
+
+// ---- masks: activation (softmax across speakers) times w, in place over the gen_masks output [M][spk N] ----------------------
+__global__ __launch_bounds__(256) void tas_mask_kernel(float* __restrict__ m, const float* __restrict__ w, long M, int N, int spk,
+                                                       int act) {
+  const long total = M * N;
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    const long row = e / N;
+    const int k = (int)(e % N);
+    float* r = m + row * (long)spk * N + k;
+    const float wv = w[e];
+    if (act == ONSSEN_TASNET_SOFTMAX) {
+      float mx = r[0];
+      for (int s = 1; s < spk; ++s) mx = fmaxf(mx, r[(long)s * N]);
+      float sum = 0.0f;
+      for (int s = 0; s < spk; ++s) sum += expf(r[(long)s * N] - mx);
+      for (int s = 0; s < spk; ++s) r[(long)s * N] = wv * (expf(r[(long)s * N] - mx) / sum);
+    } else {
+      for (int s = 0; s < spk; ++s) {
+        const float v = r[(long)s * N];
+        r[(long)s * N] = wv * (act == ONSSEN_TASNET_RELU ? fmaxf(v, 0.0f) : 1.0f / (1.0f + expf(-v)));
+      }
+    }
+  }
+}
+
+// ---- K3: decoder (ConvTranspose1d(N, 1, L, stride L/2)) ----------------------------------------------------------------------
+// grid (chunks of 16 hop-sized output blocks, utterances, speakers).  Output block j (samples [j hop, (j + 1) hop)) is covered
+// by frames j (first half of its L taps) and j - 1 (second half); there are T + 1 blocks.  The workgroup first contracts the 17
+// frames it needs over the N channels into LDS, then every output sample is written by exactly one thread.
+__global__ __launch_bounds__(256) void tas_decoder_kernel(const float* __restrict__ d, int T, int N, int L, int spk,
+                                                          const float* __restrict__ dw, const float* __restrict__ db,
+                                                          float* __restrict__ out, int S_out) {
+  __shared__ float Ps[(DEC_FRAMES + 1) * MAX_L];
+  const int b = blockIdx.y, s = blockIdx.z, n = gridDim.y, hop = L / 2;
+  const int j0 = blockIdx.x * DEC_FRAMES;
+  const long ldd = (long)spk * N;
+  for (int e = threadIdx.x; e < (DEC_FRAMES + 1) * L; e += blockDim.x) {
+    const int jj = e / L, l = e % L, f = j0 - 1 + jj;
+    float acc = 0.0f;
+    if (f >= 0 && f < T) {
+      const float* r = d + ((long)b * T + f) * ldd + (long)s * N;
+      for (int k = 0; k < N; ++k) acc += r[k] * dw[k * L + l];
+    }
+    Ps[jj * L + l] = acc;
+  }
+  __syncthreads();
+  const float bias = db[0];
+  const int i0 = j0 * hop, i1 = (j0 + DEC_FRAMES) * hop < S_out ? (j0 + DEC_FRAMES) * hop : S_out;
+  float* o = out + ((long)s * n + b) * S_out;
+  for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
+    const int j = i / hop, off = i - j * hop, jj = j - (j0 - 1);
+    float v = bias;
+    if (j < T) v += Ps[jj * L + off];                 // frame j, tap off
+    if (j >= 1) v += Ps[(jj - 1) * L + off + hop];    // frame j - 1, tap off + hop
+    o[i] = v;
+  }
+}
+
+static unsigned ew_grid(long total) { const long nb = (total + 255) / 256; return (unsigned)(nb > 16384 ? 16384 : nb < 1 ? 1 : nb); }
+
+// One 1x1 convolution: C [M][Nout] = A [M][K] W^T + b in the configured precision (image = scratch for A's x3 image).
+static int gemm(const Cfg& g, int kind, const float* A, long M, int K, const float* w32, const uint16_t* w3, const float* bias,
+                int Nout, float* C, uint16_t* image, void* stream) {
+  if (g.prec == ONSSEN_TASNET_F32 || (g.exact & kind))
+    return onssen_linear_f32(A, K, 0, 1, (int)M, K, w32, ld4(K), bias, Nout, ONSSEN_EPI_BIAS, 0, 0.0f, nullptr, C, Nout, 0, stream);
+  int rc = onssen_x3_image_f32(A, K, 0, 1, (int)M, K, image, stream);
+  if (rc) return rc;
+  const int mode = ONSSEN_EPI_BIAS | (g.prec == ONSSEN_TASNET_BF16 ? ONSSEN_EPI_BF16 : 0);
+  return onssen_linear_x3p(image, (int)M, K, w3, bias, Nout, mode, 0, 0.0f, C, 1, Nout, 0, stream);
+}
+
+}  // namespace tas
+
+// =================================================================================================
+// C ABI of the Conv-TasNet forward (include/onssen_hip.h)
+// =================================================================================================
+extern "C" {
+
+int64_t onssen_tasnet_param_floats(const int32_t* cfg_host) {
+  tas::Cfg g;
+  return tas::read_cfg(cfg_host, &g) ? tas::param_floats(g) : (int64_t)ONSSEN_E_ARG;
+}
+
+size_t onssen_tasnet_image_bytes(const int32_t* cfg_host) {
+  tas::Cfg g;
+  return tas::read_cfg(cfg_host, &g) ? tas::layout(g).total : 0;
+}
+
+int onssen_tasnet_pack_f32(const int32_t* cfg_host, const float* params, void* image, size_t image_bytes, void* stream) {
+  tas::Cfg g;
+  if (!tas::read_cfg(cfg_host, &g) || !params || !image) return ONSSEN_E_ARG;
+  const tas::Layout o = tas::layout(g);
+  if (image_bytes < o.total) return ONSSEN_E_WORKSPACE;
+  if ((reinterpret_cast<uintptr_t>(image) & 255u) != 0) return ONSSEN_E_ALIGN;
+  ONSSEN_CLEAR_ERROR();
+  char* im = static_cast<char*>(image);
+  hipStream_t st = (hipStream_t)stream;
+  const float* p = params;
+  auto f = [&](size_t off) { return reinterpret_cast<float*>(im + off); };
+  auto u = [&](size_t off) { return reinterpret_cast<uint16_t*>(im + off); };
+  auto copy = [&](long rows, int K, int ld, size_t off) {      // next rows x K floats of the flat buffer -> image (padded)
+    hipLaunchKernelGGL(tas::tas_copy_pad_kernel, dim3(tas::ew_grid(rows * ld)), dim3(256), 0, st, p, rows, K, ld, f(off));
+    p += rows * K;
+  };
+  const int ldN = tas::ld4(g.N), ldB = tas::ld4(g.B), ldH = tas::ld4(g.H);
+  copy(g.N, g.L, g.L, o.enc_w); copy(1, g.N, g.N, o.enc_b); copy(1, g.N, g.N, o.ln_g); copy(1, g.N, g.N, o.ln_b);
+  copy(g.B, g.N, ldN, o.bott_w); copy(1, g.B, g.B, o.bott_b);
+  for (int j = 0; j < g.R * g.X; ++j) {
+    const size_t k = o.blk0 + (size_t)j * o.blk_stride;
+    copy(g.H, g.B, ldB, k + o.c1_w); copy(1, g.H, g.H, k + o.c1_b); copy(1, 1, 1, k + o.alpha);
+    if (g.norm == ONSSEN_TASNET_BN) {
+      hipLaunchKernelGGL(tas::tas_fold_bn_kernel, dim3((unsigned)ceil_div(g.H, 256)), dim3(256), 0, st, p, p + g.H, p + 2 * g.H,
+                         p + 3 * g.H, g.H, f(k + o.n_a), f(k + o.n_b));
+      p += 4 * g.H;
+    } else {
+      copy(1, g.H, g.H, k + o.n_a); copy(1, g.H, g.H, k + o.n_b);
+    }
+    copy(g.H, g.P, g.P, k + o.dw_w); copy(1, g.H, g.H, k + o.dw_b);
+    copy(g.B, g.H, ldH, k + o.sc_w); copy(1, g.B, g.B, k + o.sc_b);
+  }
+  copy((long)g.spk * g.N, g.B, ldB, o.mask_w); copy(1, g.spk * g.N, g.spk * g.N, o.mask_b);
+  copy(g.N, g.L, g.L, o.dec_w); copy(1, 1, 1, o.dec_b);
+  ONSSEN_LAUNCH_CHECK();
+  // x3 images of the 1x1 weights (the split-bf16 / bf16 GEMMs' B operand) from the padded fp32 copies
+  int rc = onssen_x3_image_f32(f(o.bott_w), ldN, 0, 1, g.B, g.N, u(o.bott_x3), stream);
+  if (!rc) rc = onssen_x3_image_f32(f(o.mask_w), ldB, 0, 1, g.spk * g.N, g.B, u(o.mask_x3), stream);
+  for (int j = 0; j < g.R * g.X && !rc; ++j) {
+    const size_t k = o.blk0 + (size_t)j * o.blk_stride, k3 = o.x3_blk0 + (size_t)j * o.x3_blk_stride;
+    rc = onssen_x3_image_f32(f(k + o.c1_w), ldB, 0, 1, g.H, g.B, u(k3 + o.c1_x3), stream);
+    if (!rc) rc = onssen_x3_image_f32(f(k + o.sc_w), ldH, 0, 1, g.B, g.H, u(k3 + o.sc_x3), stream);
+  }
+  return rc;
+}
+
+size_t onssen_tasnet_workspace_bytes(const int32_t* cfg_host, int n, int S) {
+  tas::Cfg g;
+  if (!tas::read_cfg(cfg_host, &g) || n <= 0 || S < g.L) return 0;
+  return tas::ws_layout(g, n, S).total;
+}
+
+int onssen_tasnet_forward_f32(const int32_t* cfg_host, const void* image, const float* x, int n, int S, int64_t x_stride,
+                              float* out, void* ws, size_t ws_bytes, void* stream) {
+  tas::Cfg g;
+  if (!tas::read_cfg(cfg_host, &g) || !image || !x || !out || !ws || n <= 0 || S < g.L || x_stride < S) return ONSSEN_E_ARG;
+  const tas::Layout o = tas::layout(g);
+  const tas::Ws w = tas::ws_layout(g, n, S);
+  if (ws_bytes < w.total) return ONSSEN_E_WORKSPACE;
+  if ((reinterpret_cast<uintptr_t>(image) & 255u) != 0 || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0) return ONSSEN_E_ALIGN;
+  const int hop = g.L / 2, T = (S - g.L) / hop + 1, S_out = (T - 1) * hop + g.L;
+  const long M = (long)n * T;
+  if (M > 0x7fffffffL / 4) return ONSSEN_E_ARG;
+  ONSSEN_CLEAR_ERROR();
+  hipStream_t st = (hipStream_t)stream;
+  const char* im = static_cast<const char*>(image);
+  char* wb = static_cast<char*>(ws);
+  auto fi = [&](size_t off) { return reinterpret_cast<const float*>(im + off); };
+  auto ui = [&](size_t off) { return reinterpret_cast<const uint16_t*>(im + off); };
+  float *bw = reinterpret_cast<float*>(wb + w.w), *be = reinterpret_cast<float*>(wb + w.e), *bx = reinterpret_cast<float*>(wb + w.x),
+        *bc = reinterpret_cast<float*>(wb + w.c), *bt = reinterpret_cast<float*>(wb + w.t);
+  uint16_t* img = reinterpret_cast<uint16_t*>(wb + w.img);
+  double* part = reinterpret_cast<double*>(wb + w.st);
+  float* rstat = reinterpret_cast<float*>(wb + w.st);
+  // K1: encoder + LayerN_S, then the bottleneck
+  hipLaunchKernelGGL(tas::tas_encoder_kernel, dim3((unsigned)ceil_div((int)M, 4)), dim3(256), 0, st, x, (long)x_stride, T, M, g.N,
+                     g.L, fi(o.enc_w), fi(o.enc_b), fi(o.ln_g), fi(o.ln_b), bw, be);
+  ONSSEN_LAUNCH_CHECK();
+  int rc = tas::gemm(g, ONSSEN_TASNET_EXACT_BOTTLENECK, be, M, g.N, fi(o.bott_w), ui(o.bott_x3), fi(o.bott_b), g.B, bx, img, stream);
+  if (rc) return rc;
+  const int nch = ceil_div(T, tas::ROWS_PER_CHUNK);
+  for (int j = 0; j < g.R * g.X; ++j) {
+    const size_t k = o.blk0 + (size_t)j * o.blk_stride, k3 = o.x3_blk0 + (size_t)j * o.x3_blk_stride;
+    const int dil = 1 << (j % g.X);
+    const int pad_l = g.causal ? dil * (g.P - 1) : dil * (g.P - 1) / 2;
+    rc = tas::gemm(g, ONSSEN_TASNET_EXACT_CONV1X1, bx, M, g.B, fi(k + o.c1_w), ui(k3 + o.c1_x3), fi(k + o.c1_b), g.H, bc, img, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tas::tas_prelu_stats_kernel, dim3((unsigned)nch, (unsigned)n), dim3(256), 0, st, bc, T, g.H, fi(k + o.alpha),
+                       g.norm, part, rstat);
+    hipLaunchKernelGGL(tas::tas_dwconv_kernel, dim3((unsigned)ceil_div(T, tas::DW_ROWS), (unsigned)n), dim3(256), 0, st, bc, T, g.H,
+                       g.P, dil, pad_l, g.norm, part, nch, rstat, fi(k + o.n_a), fi(k + o.n_b), fi(k + o.dw_w), fi(k + o.dw_b), be);
+    ONSSEN_LAUNCH_CHECK();
+    rc = tas::gemm(g, ONSSEN_TASNET_EXACT_SC_CONV, be, M, g.H, fi(k + o.sc_w), ui(k3 + o.sc_x3), fi(k + o.sc_b), g.B, bt, img, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tas::tas_residual_kernel, dim3(tas::ew_grid(M * g.B)), dim3(256), 0, st, bx, bt, M * g.B);
+    ONSSEN_LAUNCH_CHECK();
+  }
+  rc = tas::gemm(g, ONSSEN_TASNET_EXACT_MASKS, bx, M, g.B, fi(o.mask_w), ui(o.mask_x3), fi(o.mask_b), g.spk * g.N, bt, img, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(tas::tas_mask_kernel, dim3(tas::ew_grid(M * g.N)), dim3(256), 0, st, bt, bw, M, g.N, g.spk, g.act);
+  hipLaunchKernelGGL(tas::tas_decoder_kernel, dim3((unsigned)ceil_div(T + 1, tas::DEC_FRAMES), (unsigned)n, (unsigned)g.spk),
+                     dim3(256), 0, st, bt, T, g.N, g.L, g.spk, fi(o.dec_w), fi(o.dec_b), out, S_out);
+  ONSSEN_LAUNCH_CHECK();
+  return ONSSEN_OK;
+}
+
+}  // extern "C"

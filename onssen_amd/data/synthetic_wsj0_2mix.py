@@ -11,6 +11,7 @@ the host and yields ``(input_list, label_list)``.  There is no corpus here, so u
     "chimera"   [feature_mix] , [one_hot, mag_mix, mag_s1, mag_s2]
     "chimera++" [feature_mix] , [one_hot, mag_mix, mag_s1, mag_s2, cos_s1, cos_s2]
     "phase"     [feature_mix, phase_mix] , [one_hot, mag_mix, mag_s1, mag_s2, phase_s1, phase_s2]
+    "conv-tasnet", "lstm-tasnet"   time-domain chunks (data/time_domain.py): [mix] , [s1, s2]
 
 ``one_hot`` is float64 like upstream's (np.zeros default, feature_utils.py:86; the losses cast).  Partition "tt" follows
 the EVALUATION contract (wsj0_2mix_eval_dataset, wsj0_2mix.py:166-245): whole utterances, batch 1,
@@ -21,6 +22,7 @@ import torch
 
 from ..features import stft_logmag, training_labels
 from ..synthetic import synth_mixture
+from . import time_domain
 
 
 class SyntheticWsj02mix:
@@ -28,6 +30,13 @@ class SyntheticWsj02mix:
         fo = feature_options
         g = (lambda k: fo[k]) if isinstance(fo, dict) else (lambda k: getattr(fo, k))
         self.model_name = model_name
+        self.device = torch.device(device if device is not None else "cuda:0")
+        self.num_batches = num_batches
+        self.partition = partition
+        self.seed = seed + {"tr": 0, "cv": 10_000, "tt": 20_000}.get(partition, 30_000)
+        if model_name in time_domain.MODELS:
+            self.batch_size, self.sampling_rate, self.chunk_size = time_domain.options_of(model_name, fo)
+            return
         self.batch_size, self.frame_length = int(g("batch_size")), int(g("frame_length"))
         self.sampling_rate, self.window_size, self.hop_size = int(g("sampling_rate")), int(g("window_size")), int(g("hop_size"))
         self.db_threshold = float(g("db_threshold"))
@@ -39,6 +48,20 @@ class SyntheticWsj02mix:
 
     def __len__(self):
         return self.num_batches
+
+    def _iter_time_domain(self):
+        C = self.chunk_size
+        if self.partition == "tt":          # whole utterances of different lengths (the first one a multiple of 32 when C is)
+            for it in range(self.num_batches):
+                mix, s1, s2 = synth_mixture(self.seed + it, C + 7 * it, self.sampling_rate, return_sources=True)
+                yield time_domain.eval_item(mix, s1, s2, self.device)
+            return
+        rng = np.random.default_rng(self.seed)
+        B = self.batch_size
+        for it in range(self.num_batches):  # lengths from 3/4 to 5/4 of a chunk: some utterances are cropped, some padded
+            lens = rng.integers(C * 3 // 4, C * 5 // 4 + 1, B)
+            utts = [synth_mixture(self.seed + it * B + b, int(lens[b]), self.sampling_rate, return_sources=True) for b in range(B)]
+            yield time_domain.training_batch(utts, C, rng, self.device)
 
     def _iter_eval(self):
         for it in range(self.num_batches):
@@ -54,6 +77,9 @@ class SyntheticWsj02mix:
             yield [logmag], [ri[..., 0].contiguous(), ri[..., 1].contiguous(), sig_ref]
 
     def __iter__(self):
+        if self.model_name in time_domain.MODELS:
+            yield from self._iter_time_domain()
+            return
         if self.partition == "tt":
             yield from self._iter_eval()
             return

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from ..features import stft_logmag, training_labels
+from . import time_domain
 
 
 def read_wav(fn):
@@ -112,9 +113,18 @@ class Wsj02mixFiles:
     def __init__(self, model_name, feature_options, partition="tr", device="cuda:0", shuffle=None, seed=None):
         fo = feature_options
         g = (lambda k: fo[k]) if isinstance(fo, dict) else (lambda k: getattr(fo, k))
-        if model_name not in ("dc", "chimera", "chimera++", "phase"):
+        if model_name not in ("dc", "chimera", "chimera++", "phase") + time_domain.MODELS:
             raise ValueError(f"unknown model_name {model_name!r}")
         self.model_name = model_name
+        if model_name in time_domain.MODELS:     # time-domain chunks (data/time_domain.py): no STFT settings
+            self.batch_size, self.sampling_rate, self.chunk_size = time_domain.options_of(model_name, fo)
+            self.device = torch.device(device if device is not None else "cuda:0")
+            self.partition = partition
+            self.file_list = sorted(glob.glob(os.path.join(g("data_path"), "wav8k", "min", partition, "mix", "*.wav")))
+            self.shuffle = (partition != "tt") if shuffle is None else shuffle
+            self.rng = np.random.default_rng(seed)
+            self._headers = {}
+            return
         self.batch_size, self.frame_length = int(g("batch_size")), int(g("frame_length"))
         self.sampling_rate, self.window_size, self.hop_size = int(g("sampling_rate")), int(g("window_size")), int(g("hop_size"))
         self.db_threshold = float(g("db_threshold"))
@@ -276,7 +286,20 @@ class Wsj02mixFiles:
             stop.set()
             th.join()                              # (bounded: every put gives up within 0.1 s of `stop`, a batch read is finite)
 
+    def _iter_time_domain(self):
+        if self.partition == "tt":
+            for fn in self.file_list:
+                yield time_domain.eval_item(*(_load(f, self.sampling_rate) for f in self._sources(fn)), self.device)
+            return
+        order = self.rng.permutation(len(self.file_list)) if self.shuffle else np.arange(len(self.file_list))
+        for i in range(0, len(order), self.batch_size):
+            utts = [[_load(f, self.sampling_rate) for f in self._sources(self.file_list[j])] for j in order[i:i + self.batch_size]]
+            yield time_domain.training_batch(utts, self.chunk_size, self.rng, self.device)
+
     def __iter__(self):
+        if self.model_name in time_domain.MODELS:
+            yield from self._iter_time_domain()
+            return
         if self.partition == "tt":
             yield from self._iter_eval()
             return

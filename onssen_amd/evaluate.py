@@ -320,3 +320,22 @@ class tester_chimera(tester):
         ri, sig_ref = _mix_ri(label)
         masks = torch.stack([mask_A, mask_B], -1)
         return mask_istft(ri, masks, self.hop_size, sig_ref.shape[-1], frames=frames, lengths=lengths), sig_ref.float()
+
+
+class tester_tasnet(tester):
+    """egs/wsj0-2mix/tasnet/evaluate.py:11-29: the loader yields ``[mix (1, S')]``, ``[sig_ref (1, C, S')]`` per utterance and
+    ConvTasNet's outputs are the estimates, cut to the reference's length.  ``eval()`` returns the mean SI-SDR.  Only the
+    reference's loop (``batch=1``) is supported: gLN normalises over every frame of a row, so a zero-padded row of a ragged
+    batch would not give the per-utterance result."""
+
+    def get_est_sig(self, input, label, output):
+        sig_ref, = label
+        batch, num_spk, n = sig_ref.shape           # estimates cut to the reference's length (S_out >= n)
+        sig_est = torch.stack([output[i][..., :n].reshape(batch, n) for i in range(num_spk)], dim=1).float()
+        return sig_est, sig_ref
+
+    def eval(self, window=8, batch=1, bucket=1):
+        if int(batch) > 1:
+            raise NotImplementedError("tester_tasnet: batch > 1 is not supported -- gLN over a zero-padded row is not the "
+                                      "per-utterance result; evaluate one utterance per forward (batch=1)")
+        return super().eval(window=window, batch=1, bucket=1)

@@ -254,3 +254,41 @@ def loss_chimera_psa(output, label):
         t2 = torch.min(mag_mix, torch.relu(mag_s2 * cos_s2))
         lm = _mask_term(mask_A, mask_B, mag_mix, t1, t2)
     return le * 0.975 + lm * 0.025
+
+
+# ---- time-domain losses of Conv-TasNet (onssen/loss/loss_e2e.py:7-87) ------------------------------------------------------
+# Reductions used in training: PyTorch ops, same placement of eps, zero mean and permutation search as the reference.
+
+def SI_SNR(_s, s, zero_mean=True):
+    """SI-SNR in dB of one estimate ``_s`` against one reference ``s`` (1-D tensors), no eps (loss_e2e.py:7-23)."""
+    est, ref = (_s - _s.mean(), s - s.mean()) if zero_mean else (_s, s)
+    target = (est * ref).sum() * ref / ref.norm() ** 2          # projection of the estimate on the reference
+    return 20 * torch.log10(target.norm() / (est - target).norm())
+
+
+def permute_SI_SNR(_s_lists, s_lists):
+    """The largest speaker-averaged SI_SNR over all assignments of estimates to references (loss_e2e.py:26-43)."""
+    from itertools import permutations
+    k = len(_s_lists)
+    return max(sum(SI_SNR(_s_lists[i], s_lists[p[i]]) for i in range(k)) / k for p in permutations(range(k)))
+
+
+def sisnr(x, s, eps=1e-8):
+    """Per-row SI-SNR in dB of x against s, both (N, S), eps as in loss_e2e.py:46-69: added to the squared reference norm, to
+    the noise norm and to the ratio inside the logarithm."""
+    if x.shape != s.shape:
+        raise RuntimeError(f"sisnr: shapes differ, {tuple(x.shape)} vs {tuple(s.shape)}")
+    est = x - x.mean(dim=-1, keepdim=True)
+    ref = s - s.mean(dim=-1, keepdim=True)
+    scale = (est * ref).sum(dim=-1, keepdim=True) / (ref.norm(dim=-1, keepdim=True) ** 2 + eps)
+    target = scale * ref
+    return 20 * torch.log10(eps + target.norm(dim=-1) / ((est - target).norm(dim=-1) + eps))
+
+
+def si_snr_loss(ests, refs):
+    """Negative SI-SNR training loss (loss_e2e.py:72-87): per utterance the speaker-averaged sisnr of the best assignment of
+    estimates to references, summed over the batch and divided by its size."""
+    from itertools import permutations
+    k = len(refs)
+    per_perm = torch.stack([sum(sisnr(ests[i], refs[p[i]]) for i in range(k)) / k for p in permutations(range(k))])
+    return -per_perm.max(dim=0).values.sum() / refs[0].shape[0]

@@ -5,5 +5,6 @@ from .chimera import chimera
 from .deep_clustering import deep_clustering
 from .enhancement import enhance
 from .phase_network import phase_net
+from .tasnet import ConvTasNet
 
-__all__ = ["chimera", "deep_clustering", "enhance", "phase_net"]
+__all__ = ["chimera", "deep_clustering", "enhance", "phase_net", "ConvTasNet"]

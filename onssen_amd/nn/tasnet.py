@@ -1,0 +1,219 @@
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import _abi, options
+from ._core import (PackedWeightsMixin, _Workspaces, _park_if_captured, _stream, _version_key, needs_graph, precision,
+                    require_device, use_hip_path)
+from ..hip import get_lib
+
+_NORMS = {"gln": _abi.TASNET_GLN, "cln": _abi.TASNET_CLN, "bn": _abi.TASNET_BN}
+_ACTS = {"relu": _abi.TASNET_RELU, "sigmoid": _abi.TASNET_SIGMOID, "softmax": _abi.TASNET_SOFTMAX}
+_PRECS = {"f32": _abi.TASNET_F32, "bf16x3": _abi.TASNET_BF16X3, "bf16": _abi.TASNET_BF16}
+
+
+class GlobalLayerNorm(nn.Module):
+    """gLN of the reference (onssen/nn/tasnet.py:5-44): per-utterance mean and biased variance over all (channel, frame)
+    pairs, eps inside the square root, weight and bias shaped (C, 1)."""
+
+    def __init__(self, dim, eps=1e-05):
+        super().__init__()
+        self.dim, self.eps = dim, eps
+        self.weight = nn.Parameter(torch.ones(dim, 1))
+        self.bias = nn.Parameter(torch.zeros(dim, 1))
+
+    def forward(self, x):                      # x: n x C x T
+        if x.dim() != 3:
+            raise RuntimeError("GlobalLayerNorm accepts 3D tensors")
+        mean = torch.mean(x, (1, 2), keepdim=True)
+        var = torch.mean((x - mean) ** 2, (1, 2), keepdim=True)
+        return self.weight * (x - mean) / torch.sqrt(var + self.eps) + self.bias
+
+
+class CumulativeLayerNorm(nn.LayerNorm):
+    """cLN of the reference (tasnet.py:47-67): LayerNorm over the channels of each frame."""
+
+    def forward(self, x):                      # x: n x C x T
+        return super().forward(x.transpose(1, 2)).transpose(1, 2)
+
+
+def _select_norm(norm, dim):
+    if norm == "gln":
+        return GlobalLayerNorm(dim)
+    if norm == "cln":
+        return CumulativeLayerNorm(dim)
+    return nn.BatchNorm1d(dim)
+
+
+class Conv1DBlock(nn.Module):
+    """One separation block (tasnet.py:126-163).  PReLU_2 and norm_2 are parameters of the reference's block that its forward
+    never uses: they are kept so that checkpoints load, and stay out of the computation."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, dilation, norm, causal):
+        super().__init__()
+        self.conv1x1 = nn.Conv1d(in_channels, out_channels, 1)
+        self.PReLU_1 = nn.PReLU()
+        self.norm_1 = _select_norm(norm, out_channels)
+        self.pad = dilation * (kernel_size - 1) if causal else dilation * (kernel_size - 1) // 2
+        self.dwconv = nn.Conv1d(out_channels, out_channels, kernel_size, groups=out_channels, padding=self.pad, dilation=dilation)
+        self.PReLU_2 = nn.PReLU()
+        self.norm_2 = _select_norm(norm, out_channels)
+        self.Sc_conv = nn.Conv1d(out_channels, in_channels, 1, bias=True)
+        self.causal = causal
+
+    def forward(self, x):
+        c = self.norm_1(self.PReLU_1(self.conv1x1(x)))
+        c = self.dwconv(c)
+        if self.causal:
+            c = c[:, :, :-self.pad]
+        return x + self.Sc_conv(c)
+
+
+class ConvTasNet(PackedWeightsMixin, nn.Module):
+    """Drop-in for onssen.nn.ConvTasNet (onssen/nn/tasnet.py:166-264): same constructor, defaults, submodule / parameter names
+    and shapes, and forward contract.
+
+    forward([x]) with x (S,) or (n, S) -> list of ``num_spks`` tensors, each torch.squeeze-d as upstream: (S_out,) for n = 1,
+    (n, S_out) otherwise; T = (S - L) // (L/2) + 1 frames, S_out = (T - 1) L/2 + L (trailing samples are dropped).
+
+    In eval mode without autograd, on ROCm tensors: the HIP forward (csrc/tasnet.inc) -- the encoder + LayerNorm, every 1x1
+    convolution as a row GEMM (exact fp32 under ``precision`` f32 and bf16x3, plain bf16 products under the opt-in bf16: see
+    EXACT_KINDS), PReLU + norm statistics, the normalised
+    dilated depthwise convolution, the masks and the overlap-add decoder.  A shape it cannot run raises (odd L, L > 64,
+    N > 1024, P > 32, an even P without ``causal``, more than 8 speakers); nothing falls back to ATen.
+
+    Training (train mode, or a gradient needed) is autograd over PyTorch ops on the ROCm device: Conv-TasNet training does
+    NOT run on HIP kernels yet.  A CPU tensor raises unless ONSSEN_CPU_AUTOGRAD=1 (test scaffolding) is set."""
+
+    def __init__(self, N=512, L=16, B=128, H=512, P=3, X=8, R=3, norm="gln", num_spks=2, activate="relu", causal=False,
+                 **hip_options):
+        super().__init__()
+        options.constructor_options(type(self).__name__, hip_options)
+        if norm not in _NORMS:
+            raise ValueError(f"norm must be one of {sorted(_NORMS)}, got {norm!r}")
+        if activate not in _ACTS:
+            raise KeyError(activate)
+        self.N, self.L, self.B, self.H, self.P, self.X, self.R = N, L, B, H, P, X, R
+        self.norm, self.num_spks, self.activation_type, self.causal = norm, num_spks, activate, bool(causal)
+        self.encoder = nn.Conv1d(1, N, L, stride=L // 2, padding=0)
+        self.LayerN_S = CumulativeLayerNorm(N)
+        self.BottleN_S = nn.Conv1d(N, B, 1)
+        self.separation = nn.Sequential(*[
+            nn.Sequential(*[Conv1DBlock(B, H, P, 2 ** x, norm, causal) for x in range(X)]) for _ in range(R)])
+        self.gen_masks = nn.Conv1d(B, num_spks * N, 1)
+        self.decoder = nn.ConvTranspose1d(N, 1, L, stride=L // 2)
+        self._ws = _Workspaces()
+        self._init_packed_hooks()
+        self._image = None        # (key, image tensor)
+
+    # ---- HIP path ---------------------------------------------------------------------------------------------------
+    def hip_limits(self):
+        """Reasons the HIP forward cannot run this configuration (empty: it can)."""
+        why = []
+        if self.L % 2 or not 2 <= self.L <= 64:
+            why.append(f"L = {self.L}: the HIP forward needs an even L in [2, 64]")
+        if self.N > 1024:
+            why.append(f"N = {self.N} > 1024 (encoder: one wave per frame, 16 channels per lane)")
+        if self.P > 32:
+            why.append(f"P = {self.P} > 32")
+        if self.P % 2 == 0 and not self.causal:
+            why.append(f"P = {self.P} is even without causal: the reference's block changes the frame count there")
+        if self.num_spks > 8:
+            why.append(f"num_spks = {self.num_spks} > 8")
+        if self.X > 30:
+            why.append(f"X = {self.X} > 30")
+        return why
+
+    # 1x1 convolutions kept on exact fp32 per precision (ONSSEN_TASNET_EXACT_* bits, include/onssen_hip.h).  bf16x3 keeps all four
+    # kinds there: split-bf16 products (~1e-5 relative per dot product) compound over the 50 chained GEMMs of the recipe to a
+    # relative L2 of 1.8e-5 at the output (measured, MI355X, 3 x 32 000), outside the 1e-5 contract, and no subset of the kinds
+    # brings it back with margin (every kind contributes about equally: profiles/tasnet_exact_probe.jsonl); exact fp32 costs 12 %
+    # of the forward there (the narrow GEMMs are not what bounds it).  bf16 (opt-in, bf16-grade) keeps plain bf16 products.
+    EXACT_KINDS = {"f32": 0, "bf16x3": 15, "bf16": 0}
+
+    def _cfg(self, prec):
+        return _abi.Lib.tasnet_cfg(self.N, self.L, self.B, self.H, self.P, self.X, self.R, _NORMS[self.norm], self.num_spks,
+                                   _ACTS[self.activation_type], self.causal, _PRECS[prec] | (self.EXACT_KINDS[prec] << 8))
+
+    def _packed_params(self):
+        ts = [self.encoder.weight, self.encoder.bias, self.LayerN_S.weight, self.LayerN_S.bias, self.BottleN_S.weight,
+              self.BottleN_S.bias]
+        for rep in self.separation:
+            for blk in rep:
+                ts += [blk.conv1x1.weight, blk.conv1x1.bias, blk.PReLU_1.weight, blk.norm_1.weight, blk.norm_1.bias]
+                if self.norm == "bn":
+                    ts += [blk.norm_1.running_mean, blk.norm_1.running_var]
+                ts += [blk.dwconv.weight, blk.dwconv.bias, blk.Sc_conv.weight, blk.Sc_conv.bias]
+        return ts + [self.gen_masks.weight, self.gen_masks.bias, self.decoder.weight, self.decoder.bias]
+
+    def _get_image(self, cfg):
+        ts = self._packed_params()
+        key = _version_key(ts)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._image is not None and self._image[0] == key:
+            self._in_graph = getattr(self, "_in_graph", False) or capturing
+            return self._image[1]
+        _park_if_captured(self, ("_image",))
+        self._in_graph = capturing
+        lib = get_lib()
+        dev = ts[0].device
+        flat = torch.cat([t.detach().reshape(-1).float() for t in ts]).contiguous()
+        assert flat.numel() == lib.tasnet_param_floats(cfg)
+        nb = lib.tasnet_image_bytes(cfg)
+        image = torch.empty(nb, dtype=torch.uint8, device=dev)
+        lib.tasnet_pack(cfg, flat.data_ptr(), image.data_ptr(), nb, _stream())
+        self._image = (key, image, flat)            # flat stays alive until the stream-ordered pack has read it
+        return image
+
+    def _hip_forward(self, x):
+        why = self.hip_limits()
+        if why:
+            raise RuntimeError("ConvTasNet: the HIP forward cannot run this configuration: " + "; ".join(why))
+        require_device(x, "ConvTasNet")
+        n, S = x.shape
+        if S < self.L:
+            raise RuntimeError(f"ConvTasNet: {S} samples is shorter than one encoder frame (L = {self.L})")
+        lib = get_lib()
+        cfg = self._cfg(precision())
+        image = self._get_image(cfg)
+        x = x.float()
+        if x.stride(1) != 1 or (n > 1 and x.stride(0) < S):
+            x = x.contiguous()
+        x_stride = x.stride(0) if n > 1 else S          # a size-1 batch dimension may carry any stride
+        hop = self.L // 2
+        T = (S - self.L) // hop + 1
+        S_out = (T - 1) * hop + self.L
+        nb = lib.tasnet_workspace_bytes(cfg, n, S)
+        ws = self._ws.get(("tasnet", str(x.device), n, S), nb, x.device)
+        out = torch.empty(self.num_spks, n, S_out, device=x.device, dtype=torch.float32)
+        lib.tasnet_forward(cfg, image.data_ptr(), x.data_ptr(), n, S, x_stride, out.data_ptr(), ws.data_ptr(), nb, _stream())
+        return [torch.squeeze(out[s]) for s in range(self.num_spks)]
+
+    # ---- forward ------------------------------------------------------------------------------------------------------
+    def forward(self, input):
+        x, = input
+        if x.dim() >= 3:
+            raise RuntimeError(f"ConvTasNet accepts 1/2D tensors as input, but got {x.dim()}D")
+        if x.dim() == 1:
+            x = torch.unsqueeze(x, 0)
+        if use_hip_path(self) and not needs_graph(x):
+            return self._hip_forward(x)
+        return self._autograd_forward(x)
+
+    def _autograd_forward(self, x):
+        """Training path: autograd over PyTorch ops (ROCm device only; a CPU tensor needs ONSSEN_CPU_AUTOGRAD=1)."""
+        if not x.is_cuda and options.get("cpu_autograd") != "1":
+            raise RuntimeError("onssen_amd: ConvTasNet needs tensors on a ROCm device; there is no CPU fallback "
+                               "(ONSSEN_CPU_AUTOGRAD=1 is test scaffolding, never a product path)")
+        w = self.encoder(x.unsqueeze(1))
+        e = self.BottleN_S(self.LayerN_S(w))
+        e = self.separation(e)
+        m = self.gen_masks(e)
+        m = torch.stack(torch.chunk(m, chunks=self.num_spks, dim=1), dim=0)
+        if self.activation_type == "relu":
+            m = F.relu(m)
+        elif self.activation_type == "sigmoid":
+            m = torch.sigmoid(m)
+        else:
+            m = torch.softmax(m, dim=0)
+        return [torch.squeeze(self.decoder(w * m[i])) for i in range(self.num_spks)]

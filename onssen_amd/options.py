@@ -9,6 +9,9 @@ for optional keys such as ``precision`` / ``world_size`` on that surface).  Ever
   * in the environment (``ONSSEN_*``): an environment variable that is SET always wins -- it is the operator's override for
     one run, and what the tools and tests use.
 
+``nn.ConvTasNet`` honours ``precision`` only (f32 and bf16x3 both run its 1x1 convolutions on exact fp32, bf16 on plain bf16
+products); its training runs on ATen autograd, not on HIP kernels.
+
 A reference config without any of these keys loads unchanged (tests/test_config_surface.py).  The settings are per process
 (one process drives one GPU), not per model.  Debug-build knobs of the native library (``ONSSEN_KNOB_INT`` in
 csrc/onssen_hip.hip; compiled out of the shipped build) are not listed here.

@@ -1,0 +1,110 @@
+#!/usr/bin/env python
+"""Timing of the ConvTasNet forward on one GPU: the HIP forward (graph replay, warmed up, median of >= 20 device-event timed
+replays) against the same module's ATen forward with the same weights, for each precision, at the recipe shape (3 x 32 000)
+and a throughput shape (32 x 32 000).  One JSON line per shape: ms per forward, x real time, the ATen / HIP ratio, the
+algorithmic GFLOP and bytes, and the max error of the timed step against tests/tasnet_ref.py (the recipe shape; the throughput
+shape is checked on its first 2 utterances).  Usage: python tools/tasnet_bench.py [--reps 20] [--out FILE]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from onssen_amd import nn as onn          # noqa: E402
+from tests import tasnet_ref             # noqa: E402
+
+
+def gflop_bytes(c, n, S):
+    """Algorithmic work of one forward (2 flop per multiply-add) and the fp32 bytes its unfused stages move."""
+    T = (S - c["L"]) // (c["L"] // 2) + 1
+    N, B, H, P, blocks, spk, L = c["N"], c["B"], c["H"], c["P"], c["R"] * c["X"], c["num_spks"], c["L"]
+    per_frame = N * L + N * B + blocks * (B * H + H * P + H * B) + B * spk * N + spk * N * L
+    rows = n * T
+    byts = 4 * rows * (2 * N + B + blocks * (B + 4 * H + 3 * B) + spk * N * 2 + spk * N) + 4 * n * S
+    return 2.0 * per_frame * rows / 1e9, float(byts)
+
+
+def time_graph(fn, reps):
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(3):
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = fn()
+    for _ in range(3):
+        g.replay()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        g.replay()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts)), out
+
+
+def time_eager(fn, reps):
+    for _ in range(2):
+        fn()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts)), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--shapes", default="3x32000,32x32000")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    c = tasnet_ref.RECIPE
+    sd = tasnet_ref.make_state(c, seed=11)
+    m = onn.ConvTasNet(**c)
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    m = m.to(dev).eval()
+    lines = []
+    for shp in a.shapes.split(","):
+        n, S = (int(v) for v in shp.split("x"))
+        x = (0.1 * np.random.default_rng(5).standard_normal((n, S))).astype(np.float32)
+        xd = torch.from_numpy(x).to(dev)
+        ref = np.stack(tasnet_ref.forward(sd, x[:min(n, 3)], c))
+        gf, byts = gflop_bytes(c, n, S)
+        rec = {"shape": [n, S], "gflop": round(gf, 2), "bytes_unfused": byts, "audio_s": n * S / 8000.0}
+        with torch.no_grad():
+            ms_aten, out_aten = time_eager(lambda: m._autograd_forward(xd), max(5, a.reps // 4))
+            oa = np.stack([o.cpu().numpy() for o in out_aten])[:, :min(n, 3)]
+            rec["aten_ms"] = round(ms_aten, 3)
+            rec["aten_err"] = float(np.abs(oa - ref).max())
+            for prec in ("f32", "bf16x3", "bf16"):
+                os.environ["ONSSEN_PRECISION"] = prec
+                ms, out = time_graph(lambda: m([xd]), a.reps)
+                o = np.stack([t.cpu().numpy() for t in out])[:, :min(n, 3)]
+                rec[prec] = {"ms": round(ms, 3), "x_realtime": round(rec["audio_s"] / (ms / 1e3), 1),
+                             "aten_over_hip": round(ms_aten / ms, 2), "tflops": round(gf / ms, 2),
+                             "max_err": float(np.abs(o - ref).max())}
+        os.environ.pop("ONSSEN_PRECISION", None)
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+    if a.out:
+        with open(a.out, "w") as f:
+            for r in lines:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
