@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ONSSEN_ABI_VERSION 14   /* 14 (additions, no signature changed): onssen_tasnet_* (the Conv-TasNet separation forward).  14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
+#define ONSSEN_ABI_VERSION 14   /* 14 (additions, no signature changed): onssen_tasnet_train_forward_f32, onssen_tasnet_backward_f32 and their two size queries (Conv-TasNet training).  14 (additions, no signature changed): onssen_tasnet_* (the Conv-TasNet separation forward).  14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
 
 #define ONSSEN_OK 0
 #define ONSSEN_E_ARG (-1)         /* invalid argument / unsupported shape */
@@ -726,6 +726,29 @@ int onssen_tasnet_pack_f32(const int32_t* cfg_host, const float* params, void* i
 size_t onssen_tasnet_workspace_bytes(const int32_t* cfg_host, int n, int S);
 int onssen_tasnet_forward_f32(const int32_t* cfg_host, const void* image, const float* x, int n, int S, int64_t x_stride,
                               float* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Conv-TasNet training: a forward that keeps what the backward needs, and the backward of the network (the gradient of every
+ * packed parameter; none with respect to the waveform).  cfg / image / x / n / S / x_stride as above.  norm = BN (batch
+ * statistics, running-statistics updates) is not offered: every entry point here answers it with ONSSEN_E_ARG (sizes: 0).
+ * train_forward: the kernels and the arithmetic of onssen_tasnet_forward_f32 -- `out` is bit-identical to it at the same
+ *   precision -- writing the block inputs, the conv1x1 outputs before PReLU, the norm statistics, the depthwise outputs, the
+ *   encoder output, its LayerNorm, the mask logits and the masked encoder output into `saved`
+ *   (onssen_tasnet_saved_bytes(cfg, n, S) bytes, 256-byte aligned, no zeroing needed); ws as for the forward.
+ * backward: d_out = d(loss)/d(out), num_spks x n x S_out contiguous; d_params = onssen_tasnet_param_floats(cfg) floats in the
+ *   order of `params`, every one of them written (not accumulated).  ws = onssen_tasnet_backward_workspace_bytes(cfg, n, S)
+ *   bytes, 256-byte aligned, no zeroing needed; `saved` and `image` are what the training forward of the same x read and
+ *   wrote.  Every contraction is exact fp32 whatever cfg's precision says (no bf16 product touches a gradient): input
+ *   gradients are onssen_linear_f32 on the transposed weights, weight and bias gradients per-row-chunk partial sums merged in
+ *   fp64 in a fixed order.  No atomics: two runs give the same bits.  Ordinary launches on `stream`, no allocation.
+ * A too-small saved / ws returns ONSSEN_E_WORKSPACE before anything is launched or written. */
+size_t onssen_tasnet_saved_bytes(const int32_t* cfg_host, int n, int S);
+int onssen_tasnet_train_forward_f32(const int32_t* cfg_host, const void* image, const float* x, int n, int S, int64_t x_stride,
+                                    float* out, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, void* stream);
+size_t onssen_tasnet_backward_workspace_bytes(const int32_t* cfg_host, int n, int S);
+int onssen_tasnet_backward_f32(const int32_t* cfg_host, const void* image, const float* x, int n, int S, int64_t x_stride,
+                               const void* saved, size_t saved_bytes, const float* d_out, float* d_params, void* ws, size_t ws_bytes,
+                               void* stream);
 
 #ifdef __cplusplus
 }

@@ -128,6 +128,10 @@ SIGNATURES = {
     "onssen_tasnet_pack_f32": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "onssen_tasnet_workspace_bytes": (_sz, [_vp, _i, _i]),
     "onssen_tasnet_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _sz, _vp]),
+    "onssen_tasnet_saved_bytes": (_sz, [_vp, _i, _i]),
+    "onssen_tasnet_train_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "onssen_tasnet_backward_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "onssen_tasnet_backward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -199,6 +203,27 @@ class Lib:
     def tasnet_forward(self, cfg, image, x, n, S, x_stride, out, ws, ws_bytes, stream):
         self.check(self.dll.onssen_tasnet_forward_f32(cfg, image, x, n, S, x_stride, out, ws, ws_bytes, stream),
                    "onssen_tasnet_forward_f32")
+
+    # ---- Conv-TasNet training ----------------------------------------------
+    def tasnet_saved_bytes(self, cfg, n, S):
+        nb = int(self.dll.onssen_tasnet_saved_bytes(cfg, n, S))
+        if nb == 0:
+            self.check(-1, "onssen_tasnet_saved_bytes")
+        return nb
+
+    def tasnet_backward_workspace_bytes(self, cfg, n, S):
+        nb = int(self.dll.onssen_tasnet_backward_workspace_bytes(cfg, n, S))
+        if nb == 0:
+            self.check(-1, "onssen_tasnet_backward_workspace_bytes")
+        return nb
+
+    def tasnet_train_forward(self, cfg, image, x, n, S, x_stride, out, saved, saved_bytes, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_tasnet_train_forward_f32(cfg, image, x, n, S, x_stride, out, saved, saved_bytes, ws, ws_bytes,
+                                                            stream), "onssen_tasnet_train_forward_f32")
+
+    def tasnet_backward(self, cfg, image, x, n, S, x_stride, saved, saved_bytes, d_out, d_params, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_tasnet_backward_f32(cfg, image, x, n, S, x_stride, saved, saved_bytes, d_out, d_params, ws,
+                                                       ws_bytes, stream), "onssen_tasnet_backward_f32")
 
     # ---- host-side wav reader (no device work) ---------------------------
     def wav_info(self, path):

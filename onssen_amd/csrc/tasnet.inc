@@ -190,8 +190,11 @@ __global__ __launch_bounds__(256) void tas_encoder_kernel(const float* __restric
 // grid (chunks of 64 frames, utterances); each wave takes every 4th frame of the chunk.
 //   gLN: fp64 (sum, sum of squares) of the chunk -> part[(b * nch + chunk) * 2 + {0, 1}] (fixed order: lanes, then waves)
 //   cLN: per frame (mean, rstd) -> rstat[row * 2 + {0, 1}] (two passes over the row, as LayerNorm)
+// SAVE (training forward): the pre-PReLU values are read from `src` and stay there; c receives PReLU(src).
+template <bool SAVE>
 __global__ __launch_bounds__(256) void tas_prelu_stats_kernel(float* __restrict__ c, int T, int H, const float* __restrict__ alpha,
-                                                              int norm, double* __restrict__ part, float* __restrict__ rstat) {
+                                                              int norm, double* __restrict__ part, float* __restrict__ rstat,
+                                                              const float* __restrict__ src) {
   __shared__ double red[4][2];
   const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int b = blockIdx.y, nch = gridDim.x;
@@ -202,7 +205,7 @@ __global__ __launch_bounds__(256) void tas_prelu_stats_kernel(float* __restrict_
     float* r = c + ((long)b * T + t) * H;
     float rs = 0.0f;
     for (int k = ln; k < H; k += 64) {
-      float v = r[k];
+      float v = SAVE ? src[((long)b * T + t) * H + k] : r[k];
       v = v >= 0.0f ? v : a * v;
       r[k] = v;
       if (norm == ONSSEN_TASNET_GLN) { s += (double)v; q += (double)v * (double)v; }
@@ -283,23 +286,26 @@ __global__ __launch_bounds__(256) void tas_residual_kernel(float* __restrict__ x
 }
 
 // ---- masks: activation (softmax across speakers) times w, in place over the gen_masks output [M][spk N] ----------------------
+// SAVE (training forward): the logits are read from `src` [M][spk N] and stay there; m receives the masked encoder output.
+template <bool SAVE>
 __global__ __launch_bounds__(256) void tas_mask_kernel(float* __restrict__ m, const float* __restrict__ w, long M, int N, int spk,
-                                                       int act) {
+                                                       int act, const float* __restrict__ src) {
   const long total = M * N;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const long row = e / N;
     const int k = (int)(e % N);
     float* r = m + row * (long)spk * N + k;
+    const float* q = SAVE ? src + row * (long)spk * N + k : r;
     const float wv = w[e];
     if (act == ONSSEN_TASNET_SOFTMAX) {
-      float mx = r[0];
-      for (int s = 1; s < spk; ++s) mx = fmaxf(mx, r[(long)s * N]);
+      float mx = q[0];
+      for (int s = 1; s < spk; ++s) mx = fmaxf(mx, q[(long)s * N]);
       float sum = 0.0f;
-      for (int s = 0; s < spk; ++s) sum += expf(r[(long)s * N] - mx);
-      for (int s = 0; s < spk; ++s) r[(long)s * N] = wv * (expf(r[(long)s * N] - mx) / sum);
+      for (int s = 0; s < spk; ++s) sum += expf(q[(long)s * N] - mx);
+      for (int s = 0; s < spk; ++s) r[(long)s * N] = wv * (expf(q[(long)s * N] - mx) / sum);
     } else {
       for (int s = 0; s < spk; ++s) {
-        const float v = r[(long)s * N];
+        const float v = q[(long)s * N];
         r[(long)s * N] = wv * (act == ONSSEN_TASNET_RELU ? fmaxf(v, 0.0f) : 1.0f / (1.0f + expf(-v)));
       }
     }
@@ -456,8 +462,8 @@ int onssen_tasnet_forward_f32(const int32_t* cfg_host, const void* image, const 
     const int pad_l = g.causal ? dil * (g.P - 1) : dil * (g.P - 1) / 2;
     rc = tas::gemm(g, ONSSEN_TASNET_EXACT_CONV1X1, bx, M, g.B, fi(k + o.c1_w), ui(k3 + o.c1_x3), fi(k + o.c1_b), g.H, bc, img, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(tas::tas_prelu_stats_kernel, dim3((unsigned)nch, (unsigned)n), dim3(256), 0, st, bc, T, g.H, fi(k + o.alpha),
-                       g.norm, part, rstat);
+    hipLaunchKernelGGL(tas::tas_prelu_stats_kernel<false>, dim3((unsigned)nch, (unsigned)n), dim3(256), 0, st, bc, T, g.H,
+                       fi(k + o.alpha), g.norm, part, rstat, (const float*)nullptr);
     hipLaunchKernelGGL(tas::tas_dwconv_kernel, dim3((unsigned)ceil_div(T, tas::DW_ROWS), (unsigned)n), dim3(256), 0, st, bc, T, g.H,
                        g.P, dil, pad_l, g.norm, part, nch, rstat, fi(k + o.n_a), fi(k + o.n_b), fi(k + o.dw_w), fi(k + o.dw_b), be);
     ONSSEN_LAUNCH_CHECK();
@@ -468,7 +474,8 @@ int onssen_tasnet_forward_f32(const int32_t* cfg_host, const void* image, const 
   }
   rc = tas::gemm(g, ONSSEN_TASNET_EXACT_MASKS, bx, M, g.B, fi(o.mask_w), ui(o.mask_x3), fi(o.mask_b), g.spk * g.N, bt, img, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(tas::tas_mask_kernel, dim3(tas::ew_grid(M * g.N)), dim3(256), 0, st, bt, bw, M, g.N, g.spk, g.act);
+  hipLaunchKernelGGL(tas::tas_mask_kernel<false>, dim3(tas::ew_grid(M * g.N)), dim3(256), 0, st, bt, bw, M, g.N, g.spk, g.act,
+                     (const float*)nullptr);
   hipLaunchKernelGGL(tas::tas_decoder_kernel, dim3((unsigned)ceil_div(T + 1, tas::DEC_FRAMES), (unsigned)n, (unsigned)g.spk),
                      dim3(256), 0, st, bt, T, g.N, g.L, g.spk, fi(o.dec_w), fi(o.dec_b), out, S_out);
   ONSSEN_LAUNCH_CHECK();

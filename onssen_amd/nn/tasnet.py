@@ -69,6 +69,95 @@ class Conv1DBlock(nn.Module):
         return x + self.Sc_conv(c)
 
 
+class _SavedSlot:
+    """One buffer of saved activations of the HIP training forward.  ``owner`` is the generation number of the forward whose
+    graph still needs it (0: free); ``gen`` counts the forwards that wrote it."""
+
+    def __init__(self, buf):
+        self.buf, self.owner, self.gen = buf, 0, 0
+
+
+class _Lease:
+    """Held by the autograd node of one training forward: gives the slot back after that node's backward, or when the graph is
+    dropped without one (a training forward under no_grad, a loss that is never differentiated)."""
+
+    def __init__(self, slot):
+        slot.gen += 1
+        slot.owner = self.gen = slot.gen
+        self.slot = slot
+
+    def release(self):
+        if self.slot.owner == self.gen:
+            self.slot.owner = 0
+
+    def valid(self):
+        return self.slot.gen == self.gen
+
+    __del__ = release
+
+
+class _TasNetTrainFunction(torch.autograd.Function):
+    """The network of ConvTasNet as ONE autograd node on HIP kernels (csrc/tasnet_bwd.inc): forward(model, x, *parameters in
+    the order of model._packed_params()) -> (num_spks, n, S_out); backward -> the parameters' gradients as views of ONE flat
+    buffer, allocated per call (autograd may keep the views as ``p.grad``, and a second backward before ``zero_grad()`` has to
+    add to them).  No gradient with respect to x.
+
+    Saved activations live in buffers the model caches per shape.  A forward takes a free one and its graph owns it until its
+    backward has run or the graph is dropped; a second forward while the first graph is alive gets a buffer of its own (two graphs
+    alive = two buffers, both kept for reuse).  Backward through a retained graph (``retain_graph=True``) works as long as no
+    later forward has taken the buffer over; after that it raises instead of differentiating somebody else's activations."""
+
+    @staticmethod
+    def forward(ctx, model, x, *params):
+        lib = get_lib()
+        cfg = model._cfg(precision())
+        image = model._get_image(cfg)
+        n, S = x.shape
+        x_stride = x.stride(0) if n > 1 else S
+        hop = model.L // 2
+        S_out = ((S - model.L) // hop) * hop + model.L
+        dev = x.device
+        nb = lib.tasnet_workspace_bytes(cfg, n, S)
+        ws = model._ws.get(("tasnet", str(dev), n, S), nb, dev)
+        sb = lib.tasnet_saved_bytes(cfg, n, S)
+        slots = model._train_saved.setdefault((str(dev), n, S), [])
+        slot = next((s for s in slots if s.owner == 0 and s.buf.numel() >= sb), None)
+        if slot is None:
+            slot = _SavedSlot(torch.empty(sb, dtype=torch.uint8, device=dev))
+            slots.append(slot)
+        ctx.lease = _Lease(slot)
+        out = torch.empty(model.num_spks, n, S_out, device=dev, dtype=torch.float32)
+        lib.tasnet_train_forward(cfg, image.data_ptr(), x.data_ptr(), n, S, x_stride, out.data_ptr(), slot.buf.data_ptr(), sb,
+                                 ws.data_ptr(), nb, _stream())
+        ctx.model, ctx.cfg, ctx.image, ctx.x, ctx.geom = model, cfg, image, x, (n, S, x_stride, sb)
+        ctx.shapes = [p.shape for p in params]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        lease, model = ctx.lease, ctx.model
+        if not lease.valid():
+            raise RuntimeError("ConvTasNet: the saved activations of this forward were taken over by a later forward "
+                               "(backward through a retained graph after its buffer was released)")
+        lib = get_lib()
+        n, S, x_stride, sb = ctx.geom
+        d_out = d_out.contiguous().float()
+        dev = d_out.device
+        nb = lib.tasnet_backward_workspace_bytes(ctx.cfg, n, S)
+        ws = model._ws.get(("tasnet_bwd", str(dev), n, S), nb, dev)
+        flat = torch.empty(lib.tasnet_param_floats(ctx.cfg), device=dev, dtype=torch.float32)
+        lib.tasnet_backward(ctx.cfg, ctx.image.data_ptr(), ctx.x.data_ptr(), n, S, x_stride, lease.slot.buf.data_ptr(), sb,
+                            d_out.data_ptr(), flat.data_ptr(), ws.data_ptr(), nb, _stream())
+        lease.release()
+        grads, at = [], 0
+        for i, shape in enumerate(ctx.shapes):
+            size = shape.numel()
+            grads.append(flat[at:at + size].view(shape) if ctx.needs_input_grad[2 + i] else None)
+            at += size
+        return (None, None, *grads)
+
+
 class ConvTasNet(PackedWeightsMixin, nn.Module):
     """Drop-in for onssen.nn.ConvTasNet (onssen/nn/tasnet.py:166-264): same constructor, defaults, submodule / parameter names
     and shapes, and forward contract.
@@ -82,8 +171,14 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
     dilated depthwise convolution, the masks and the overlap-add decoder.  A shape it cannot run raises (odd L, L > 64,
     N > 1024, P > 32, an even P without ``causal``, more than 8 speakers); nothing falls back to ATen.
 
-    Training (train mode, or a gradient needed) is autograd over PyTorch ops on the ROCm device: Conv-TasNet training does
-    NOT run on HIP kernels yet.  A CPU tensor raises unless ONSSEN_CPU_AUTOGRAD=1 (test scaffolding) is set."""
+    Training (train mode, or a parameter gradient needed) on ROCm tensors with fp32 parameters: the network's forward AND
+    backward run on HIP kernels behind one autograd node (_TasNetTrainFunction, csrc/tasnet_bwd.inc; option ``tasnet_train``,
+    default "hip"), so ``loss.backward()``, ``dist.train_step``, the fused clip + Adam and the gradient reducer work on it as on
+    any module; the training forward's output is bit-identical to the eval forward's.  The loss stays on ATen ops.
+    ``hip_train_limits()`` lists what sends a training forward to ATen autograd instead (``_autograd_forward``): what
+    ``hip_limits()`` lists, ``norm="bn"``, an input that requires a gradient, anomaly mode; double backward is not offered.
+    ``last_train_path`` ("hip" | "aten") says which path the last training forward took.  A CPU tensor raises unless
+    ONSSEN_CPU_AUTOGRAD=1 (test scaffolding) is set."""
 
     def __init__(self, N=512, L=16, B=128, H=512, P=3, X=8, R=3, norm="gln", num_spks=2, activate="relu", causal=False,
                  **hip_options):
@@ -105,6 +200,8 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
         self._ws = _Workspaces()
         self._init_packed_hooks()
         self._image = None        # (key, image tensor)
+        self._train_saved = {}    # (device, n, S) -> [_SavedSlot]: saved activations of the HIP training forward
+        self.last_train_path = None
 
     # ---- HIP path ---------------------------------------------------------------------------------------------------
     def hip_limits(self):
@@ -189,6 +286,27 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
         lib.tasnet_forward(cfg, image.data_ptr(), x.data_ptr(), n, S, x_stride, out.data_ptr(), ws.data_ptr(), nb, _stream())
         return [torch.squeeze(out[s]) for s in range(self.num_spks)]
 
+    def hip_train_limits(self, x=None):
+        """Reasons a training forward (of ``x``, if given) cannot run on the HIP training kernels (empty: it can)."""
+        why = self.hip_limits()
+        if self.norm == "bn":
+            why.append("norm = 'bn': train-mode BatchNorm (batch statistics, running-statistics updates) stays on ATen")
+        if x is not None and needs_graph(x):
+            why.append("the input requires a gradient: the HIP backward gives parameter gradients only")
+        if torch.is_anomaly_enabled():
+            why.append("autograd anomaly mode")
+        return why
+
+    def _hip_train_forward(self, x):
+        n, S = x.shape
+        if S < self.L:
+            raise RuntimeError(f"ConvTasNet: {S} samples is shorter than one encoder frame (L = {self.L})")
+        x = x.float()
+        if x.stride(1) != 1 or (n > 1 and x.stride(0) < S):
+            x = x.contiguous()
+        out = _TasNetTrainFunction.apply(self, x, *self._packed_params())
+        return [torch.squeeze(out[s]) for s in range(self.num_spks)]
+
     # ---- forward ------------------------------------------------------------------------------------------------------
     def forward(self, input):
         x, = input
@@ -198,10 +316,15 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
             x = torch.unsqueeze(x, 0)
         if use_hip_path(self) and not needs_graph(x):
             return self._hip_forward(x)
+        if (options.get("tasnet_train") == "hip" and x.is_cuda and all(p.dtype == torch.float32 for p in self._packed_params())
+                and not self.hip_train_limits(x)):
+            self.last_train_path = "hip"
+            return self._hip_train_forward(x)
+        self.last_train_path = "aten"
         return self._autograd_forward(x)
 
     def _autograd_forward(self, x):
-        """Training path: autograd over PyTorch ops (ROCm device only; a CPU tensor needs ONSSEN_CPU_AUTOGRAD=1)."""
+        """ATen training path: autograd over PyTorch ops (ROCm device only; a CPU tensor needs ONSSEN_CPU_AUTOGRAD=1)."""
         if not x.is_cuda and options.get("cpu_autograd") != "1":
             raise RuntimeError("onssen_amd: ConvTasNet needs tensors on a ROCm device; there is no CPU fallback "
                                "(ONSSEN_CPU_AUTOGRAD=1 is test scaffolding, never a product path)")

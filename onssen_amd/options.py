@@ -9,8 +9,9 @@ for optional keys such as ``precision`` / ``world_size`` on that surface).  Ever
   * in the environment (``ONSSEN_*``): an environment variable that is SET always wins -- it is the operator's override for
     one run, and what the tools and tests use.
 
-``nn.ConvTasNet`` honours ``precision`` only (f32 and bf16x3 both run its 1x1 convolutions on exact fp32, bf16 on plain bf16
-products); its training runs on ATen autograd, not on HIP kernels.
+``nn.ConvTasNet`` honours ``precision`` (f32 and bf16x3 both run its 1x1 convolutions on exact fp32, bf16 on plain bf16
+products) and ``tasnet_train``: its training forward and backward run on HIP kernels (csrc/tasnet_bwd.inc; the gradients'
+contractions are exact fp32 under every ``precision``), or on ATen autograd with ``tasnet_train = "aten"``.
 
 A reference config without any of these keys loads unchanged (tests/test_config_surface.py).  The settings are per process
 (one process drives one GPU), not per model.  Debug-build knobs of the native library (``ONSSEN_KNOB_INT`` in
@@ -88,6 +89,9 @@ TABLE = {
     "train_wgrad_rows": ("ONSSEN_TRAIN_WGRAD_ROWS", "1", _flag, "weight gradients from the row-major images the forward left"),
     "train_fused_loss": ("ONSSEN_TRAIN_FUSED_LOSS", "1", _flag, "fc_dc + normalise + loss_dc as one autograd node in train_step"),
     "train_fused_norm": ("ONSSEN_TRAIN_FUSED_NORM", "1", _flag, "fc_dc + normalise as one autograd node"),
+    "tasnet_train": ("ONSSEN_TASNET_TRAIN", "hip", _choice("hip", "aten"),
+                     "ConvTasNet training: hip = forward and backward of the network on the HIP kernels behind one autograd node "
+                     "(gln / cln; bn, an input that requires a gradient and anomaly mode go to ATen by themselves), aten = autograd over PyTorch ops"),
     "loss": ("ONSSEN_LOSS_HIP", "1", _alias({"hip": "1", "torch": "0"}), "loss kernels on the device or PyTorch ops"),
     "fused_adam": ("ONSSEN_FUSED_ADAM", "1", _flag, "build_optimizer returns utils.ClipAdam (clipping + Adam on onssen_clip_adam_f32) for device parameters"),
     "cpu_autograd": ("ONSSEN_CPU_AUTOGRAD", "0", _flag, "TEST SCAFFOLDING, off in the product: let a training forward on CPU tensors run on ATen's LSTM so that "

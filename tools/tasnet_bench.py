@@ -3,7 +3,14 @@
 replays) against the same module's ATen forward with the same weights, for each precision, at the recipe shape (3 x 32 000)
 and a throughput shape (32 x 32 000).  One JSON line per shape: ms per forward, x real time, the ATen / HIP ratio, the
 algorithmic GFLOP and bytes, and the max error of the timed step against tests/tasnet_ref.py (the recipe shape; the throughput
-shape is checked on its first 2 utterances).  Usage: python tools/tasnet_bench.py [--reps 20] [--out FILE]"""
+shape is checked on its first 2 utterances).  Usage: python tools/tasnet_bench.py [--reps 20] [--out FILE]
+
+--train: the training leg.  One step = forward + si_snr_loss + backward + clip + Adam through dist.train_step, at 3 x 32 000
+(recipe) and 16 x 32 000, ``tasnet_train`` hip against aten in the same process on the same card, interleaved step by step,
+warmed up, median and min-max of --reps device-event timed steps each, plus forward-only (network + loss) and backward-only
+splits.  One JSON line per shape (default --out with --train: profiles/tasnet_train_bench.jsonl).
+--train-profile N: N HIP training steps at the recipe shape and nothing else -- the run to put under
+``rocprofv3 --kernel-trace --stats`` (a run of its own: profiling perturbs the timing)."""
 import argparse
 import json
 import os
@@ -65,12 +72,100 @@ def time_eager(fn, reps):
     return float(np.median(ts)), out
 
 
+def _stats(ts):
+    return {"median_ms": round(float(np.median(ts)), 3), "min_ms": round(float(np.min(ts)), 3), "max_ms": round(float(np.max(ts)), 3)}
+
+
+def _timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b), out
+
+
+def train_leg(a):
+    from onssen_amd import dist, loss as L
+    from onssen_amd.utils import build_optimizer
+    dev = torch.device("cuda:0")
+    c = dict(tasnet_ref.RECIPE, activate="sigmoid")          # the shipped recipe's activation
+    sd = tasnet_ref.make_state(c, seed=11)
+    paths = ("hip", "aten")
+
+    def fresh():
+        m = onn.ConvTasNet(**c)
+        m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+        m = m.to(dev).train()
+        return m, build_optimizer(m.parameters(), {"name": "adam", "lr": 1e-3})
+
+    if a.train_profile:
+        os.environ["ONSSEN_TASNET_TRAIN"] = "hip"
+        n, S = 3, 32000
+        rng = np.random.default_rng(5)
+        xd = torch.from_numpy((0.1 * rng.standard_normal((n, S))).astype(np.float32)).to(dev)
+        refs = [torch.from_numpy((0.1 * rng.standard_normal((n, S))).astype(np.float32)).to(dev) for _ in range(c["num_spks"])]
+        m, opt = fresh()
+        for _ in range(a.train_profile):
+            dist.train_step(m, opt, L.si_snr_loss, [xd], refs)
+        torch.cuda.synchronize()
+        return
+    lines = []
+    for shp in a.shapes.split(","):
+        n, S = (int(v) for v in shp.split("x"))
+        rng = np.random.default_rng(5)
+        xd = torch.from_numpy((0.1 * rng.standard_normal((n, S))).astype(np.float32)).to(dev)
+        refs = [torch.from_numpy((0.1 * rng.standard_normal((n, S))).astype(np.float32)).to(dev) for _ in range(c["num_spks"])]
+        pair = {p: fresh() for p in paths}
+        step, fwd, bwd, loss0 = {p: [] for p in paths}, {p: [] for p in paths}, {p: [] for p in paths}, {}
+        for it in range(a.warmup + a.reps):                   # interleaved: hip, aten, hip, aten, ...
+            for p in paths:
+                os.environ["ONSSEN_TASNET_TRAIN"] = p
+                m, opt = pair[p]
+                ms, val = _timed(lambda: dist.train_step(m, opt, L.si_snr_loss, [xd], refs))
+                assert m.last_train_path == p
+                loss0.setdefault(p, val)
+                if it >= a.warmup:
+                    step[p].append(ms)
+        for it in range(a.warmup + a.reps):                   # the splits, on the weights the steps left
+            for p in paths:
+                os.environ["ONSSEN_TASNET_TRAIN"] = p
+                m, opt = pair[p]
+                m.zero_grad(set_to_none=True)
+                ms_f, loss = _timed(lambda: L.si_snr_loss(m([xd]), refs))
+                ms_b, _ = _timed(loss.backward)
+                del loss
+                if it >= a.warmup:
+                    fwd[p].append(ms_f)
+                    bwd[p].append(ms_b)
+        os.environ.pop("ONSSEN_TASNET_TRAIN", None)
+        rec = {"shape": [n, S], "reps": a.reps, "warmup": a.warmup, "audio_s": n * S / 8000.0}
+        for p in paths:
+            rec[p] = {"step": _stats(step[p]), "forward_and_loss": _stats(fwd[p]), "backward": _stats(bwd[p]), "first_loss": loss0[p]}
+        rec["aten_over_hip_step"] = round(rec["aten"]["step"]["median_ms"] / rec["hip"]["step"]["median_ms"], 2)
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+        del pair
+        torch.cuda.empty_cache()
+    out = a.out or os.path.join(ROOT, "profiles", "tasnet_train_bench.jsonl")
+    with open(out, "w") as f:
+        for r in lines:
+            f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true")
+    ap.add_argument("--train-profile", type=int, default=0)
+    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--shapes", default="3x32000,32x32000")
+    ap.add_argument("--shapes", default=None)
     a = ap.parse_args()
+    if a.train or a.train_profile:
+        a.shapes = a.shapes or "3x32000,16x32000"
+        return train_leg(a)
+    a.shapes = a.shapes or "3x32000,32x32000"
     dev = torch.device("cuda:0")
     c = tasnet_ref.RECIPE
     sd = tasnet_ref.make_state(c, seed=11)
