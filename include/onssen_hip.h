@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ONSSEN_ABI_VERSION 14   /* 14 (additions, no signature changed): onssen_tasnet_train_forward_f32, onssen_tasnet_backward_f32 and their two size queries (Conv-TasNet training).  14 (additions, no signature changed): onssen_tasnet_* (the Conv-TasNet separation forward).  14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
+#define ONSSEN_ABI_VERSION 14   /* 14 (additions, no signature changed): onssen_tasnet_forward_ragged_f32 and onssen_tasnet_ragged_workspace_bytes (Conv-TasNet over whole utterances of different lengths).  14 (additions, no signature changed): onssen_tasnet_train_forward_f32, onssen_tasnet_backward_f32 and their two size queries (Conv-TasNet training).  14 (additions, no signature changed): onssen_tasnet_* (the Conv-TasNet separation forward).  14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
 
 #define ONSSEN_OK 0
 #define ONSSEN_E_ARG (-1)         /* invalid argument / unsupported shape */
@@ -726,6 +726,28 @@ int onssen_tasnet_pack_f32(const int32_t* cfg_host, const float* params, void* i
 size_t onssen_tasnet_workspace_bytes(const int32_t* cfg_host, int n, int S);
 int onssen_tasnet_forward_f32(const int32_t* cfg_host, const void* image, const float* x, int n, int S, int64_t x_stride,
                               float* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Conv-TasNet forward over a RAGGED batch: n whole utterances of different lengths in one call.  cfg / image as above (the
+ * same image, every norm, activation and precision).
+ * lengths_host: n HOST int32 sample counts S_b, 1 <= n <= ONSSEN_TASNET_RAGGED_MAX.  x: row b holds utterance b at
+ *   x + b * x_stride; samples at and beyond S_b are never read (nothing beyond S_out_b is).  Utterance b has
+ *   T_b = (S_b - L) / (L/2) + 1 frames and S_out_b = (T_b - 1) L/2 + L output samples.
+ * out: num_spks x n rows of out_stride floats, out_stride >= max S_out_b; row (s, b) holds the estimate in [0, S_out_b) and
+ *   zeros in [S_out_b, out_stride): every float of out is written.
+ * ws: onssen_tasnet_ragged_workspace_bytes(cfg, n, lengths_host) bytes, 256-byte aligned, no zeroing needed.  Activations are
+ *   compact rows (M = sum T_b, no padded rows), so the size is that of the rectangular forward at the same number of rows and
+ *   statistics chunks: for n = 1 it EQUALS onssen_tasnet_workspace_bytes(cfg, 1, S_0).
+ * Row (s, b) is bit for bit what onssen_tasnet_forward_f32 gives for utterance b alone (n = 1, S = S_b): gLN statistics,
+ *   the depthwise convolution's zero padding and the overlap-add stop at the utterance's own last frame.  The per-utterance
+ *   table travels to the kernels by value as a kernel argument (hence the bound on n): no host synchronisation, no copy, no
+ *   atomics; ordinary launches on `stream`.  A captured graph holds the table, so it is tied to the lengths it was captured with.
+ * ONSSEN_E_ARG: n out of range, an S_b < L or > x_stride, out_stride < max S_out_b, sum T_b > 2^31 / 4. */
+#define ONSSEN_TASNET_RAGGED_MAX 64
+size_t onssen_tasnet_ragged_workspace_bytes(const int32_t* cfg_host, int n, const int32_t* lengths_host);
+int onssen_tasnet_forward_ragged_f32(const int32_t* cfg_host, const void* image, const float* x, int n,
+                                     const int32_t* lengths_host, int64_t x_stride, float* out, int64_t out_stride, void* ws,
+                                     size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Conv-TasNet training: a forward that keeps what the backward needs, and the backward of the network (the gradient of every

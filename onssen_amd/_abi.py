@@ -25,6 +25,7 @@ DC_CLUSTER_LAUNCH_PER_ITERATION = 1
 BLSTM_WS_HEADER = 32768
 TASNET_GLN, TASNET_CLN, TASNET_BN = 0, 1, 2
 TASNET_RELU, TASNET_SIGMOID, TASNET_SOFTMAX = 0, 1, 2
+TASNET_RAGGED_MAX = 64   # ONSSEN_TASNET_RAGGED_MAX: utterances of one ragged Conv-TasNet forward
 TASNET_F32, TASNET_BF16X3, TASNET_BF16 = 0, 1, 2   # ONSSEN_BLSTM_WS_HEADER_BYTES: zeroed once by the workspace owner
 
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -128,6 +129,8 @@ SIGNATURES = {
     "onssen_tasnet_pack_f32": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "onssen_tasnet_workspace_bytes": (_sz, [_vp, _i, _i]),
     "onssen_tasnet_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _sz, _vp]),
+    "onssen_tasnet_ragged_workspace_bytes": (_sz, [_vp, _i, _vp]),
+    "onssen_tasnet_forward_ragged_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
     "onssen_tasnet_saved_bytes": (_sz, [_vp, _i, _i]),
     "onssen_tasnet_train_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _sz, _vp, _sz, _vp]),
     "onssen_tasnet_backward_workspace_bytes": (_sz, [_vp, _i, _i]),
@@ -203,6 +206,21 @@ class Lib:
     def tasnet_forward(self, cfg, image, x, n, S, x_stride, out, ws, ws_bytes, stream):
         self.check(self.dll.onssen_tasnet_forward_f32(cfg, image, x, n, S, x_stride, out, ws, ws_bytes, stream),
                    "onssen_tasnet_forward_f32")
+
+    @staticmethod
+    def tasnet_lengths(lengths):
+        """Host int32 array of the sample counts of a ragged batch; keep the object alive across the call."""
+        return (C.c_int32 * len(lengths))(*[int(v) for v in lengths])
+
+    def tasnet_ragged_workspace_bytes(self, cfg, n, lengths):
+        nb = int(self.dll.onssen_tasnet_ragged_workspace_bytes(cfg, n, lengths))
+        if nb == 0:
+            self.check(-1, "onssen_tasnet_ragged_workspace_bytes")
+        return nb
+
+    def tasnet_forward_ragged(self, cfg, image, x, n, lengths, x_stride, out, out_stride, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_tasnet_forward_ragged_f32(cfg, image, x, n, lengths, x_stride, out, out_stride, ws, ws_bytes,
+                                                             stream), "onssen_tasnet_forward_ragged_f32")
 
     # ---- Conv-TasNet training ----------------------------------------------
     def tasnet_saved_bytes(self, cfg, n, S):

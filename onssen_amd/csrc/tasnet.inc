@@ -13,6 +13,13 @@
 //   tas_decoder_kernel      ConvTranspose1d(N, 1, L, stride L/2): per frame a contraction over N, then the overlap-add of the
 //                           two frames that cover each output sample, plus the bias; each output sample has exactly one owner
 // No atomics, no spinning, no allocation: the whole forward is a fixed sequence of ordinary launches on one stream.
+//
+// Ragged batches (onssen_tasnet_forward_ragged_f32): COMPACT rows -- utterance b owns rows [row[b], row[b] + T_b), no padded
+// rows exist, so the GEMMs, the residual and the mask kernel run unchanged over M = sum T_b rows.  The four kernels that know
+// where an utterance ends (encoder, statistics, depthwise convolution, decoder) have a *_ragged_kernel twin over the SAME
+// device body: the twin only finds (utterance, first frame) of its workgroup from a table of prefix sums that travels by value
+// as a kernel argument (struct Rag; host integers in, no copy, no synchronisation), so one output element is computed by the
+// same instructions in the same order as in a one-utterance rectangular run.
 // PReLU_2 / norm_2 exist upstream but the block's forward never calls them (tasnet.py:149-163): they are not packed.
 
 namespace tas {
@@ -22,6 +29,25 @@ constexpr int DW_ROWS = 32;             // depthwise convolution: frames per wor
 constexpr int DEC_FRAMES = 16;          // decoder: 16 hop-sized output blocks per workgroup
 constexpr int MAX_L = 64, MAX_N = 1024, MAX_SPK = 8, MAX_P = 32;
 constexpr float EPS = 1e-5f;            // GlobalLayerNorm, LayerNorm and BatchNorm1d defaults of the reference
+constexpr int MAX_UTT = ONSSEN_TASNET_RAGGED_MAX;   // utterances of one ragged forward (bounds the by-value table)
+
+// Table of a ragged batch: row[b] = first row of utterance b (prefix sums of T_b), blk[b] = first workgroup of utterance b in
+// the launch that receives this copy (prefix sums of that kernel's per-utterance workgroup count).  Both strictly increasing.
+struct Rag {
+  int n;
+  int row[MAX_UTT + 1];
+  int blk[MAX_UTT + 1];
+};
+
+// largest b with pre[b] <= v (pre[0] = 0 <= v < pre[n])
+__device__ __forceinline__ int rag_find(const int* pre, int n, int v) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (pre[mid] <= v) lo = mid; else hi = mid;
+  }
+  return lo;
+}
 
 struct Cfg {
   int N, L, B, H, P, X, R, norm, spk, act, causal, prec, exact;   // exact: ONSSEN_TASNET_EXACT_* kinds kept on exact fp32
@@ -92,15 +118,12 @@ struct Ws {
   size_t w, e, x, c, t, img, st, total;
 };
 
-static Ws ws_layout(const Cfg& g, int n, int S) {
+// M rows in all, nchunks gLN partial pairs in all (rectangular: n T and n ceil(T / 64))
+static Ws ws_layout_rows(const Cfg& g, size_t M, size_t nchunks) {
   Ws o;
-  const int T = (S - g.L) / (g.L / 2) + 1;
-  const size_t M = (size_t)n * T;
   const int kbmax = ceil_div(g.N > g.B ? (g.N > g.H ? g.N : g.H) : (g.B > g.H ? g.B : g.H), 32);
   const int NH = g.N > g.H ? g.N : g.H, BS = g.B > g.spk * g.N ? g.B : g.spk * g.N;
-  const size_t nch = (size_t)ceil_div(T, ROWS_PER_CHUNK);
-  const size_t st_bytes = (size_t)n * nch * 2 * sizeof(double) > M * 2 * sizeof(float) ? (size_t)n * nch * 2 * sizeof(double)
-                                                                                      : M * 2 * sizeof(float);
+  const size_t st_bytes = nchunks * 2 * sizeof(double) > M * 2 * sizeof(float) ? nchunks * 2 * sizeof(double) : M * 2 * sizeof(float);
   size_t p = 0;
   o.w = p; p += al(M * g.N * 4);
   o.e = p; p += al(M * NH * 4);
@@ -111,6 +134,11 @@ static Ws ws_layout(const Cfg& g, int n, int S) {
   o.st = p; p += al(st_bytes);
   o.total = p;
   return o;
+}
+
+static Ws ws_layout(const Cfg& g, int n, int S) {
+  const int T = (S - g.L) / (g.L / 2) + 1;
+  return ws_layout_rows(g, (size_t)n * T, (size_t)n * ceil_div(T, ROWS_PER_CHUNK));
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -149,16 +177,10 @@ __global__ __launch_bounds__(256) void tas_fold_bn_kernel(const float* __restric
 
 // ---- K1: encoder + LayerN_S -------------------------------------------------------------------------------------------------
 // One wave per frame; lane j owns channels j, j + 64, ... (N <= 1024: 16 per lane, register-resident).
-__global__ __launch_bounds__(256) void tas_encoder_kernel(const float* __restrict__ x, long x_s, int T, long M, int N, int L,
-                                                          const float* __restrict__ ew, const float* __restrict__ eb,
-                                                          const float* __restrict__ g, const float* __restrict__ be,
-                                                          float* __restrict__ w_out, float* __restrict__ e_out) {
+__device__ __forceinline__ void tas_encoder_row(const float* __restrict__ fr, long row, int N, int L, const float* __restrict__ ew,
+                                                const float* __restrict__ eb, const float* __restrict__ g,
+                                                const float* __restrict__ be, float* __restrict__ w_out, float* __restrict__ e_out) {
   const int ln = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;                               // no barrier in this kernel
-  const long b = row / T;
-  const int t = (int)(row % T);
-  const float* fr = x + b * x_s + (long)t * (L / 2);
   float v[MAX_N / 64];
   float s = 0.0f;
 #pragma unroll
@@ -186,26 +208,48 @@ __global__ __launch_bounds__(256) void tas_encoder_kernel(const float* __restric
   }
 }
 
+__global__ __launch_bounds__(256) void tas_encoder_kernel(const float* __restrict__ x, long x_s, int T, long M, int N, int L,
+                                                          const float* __restrict__ ew, const float* __restrict__ eb,
+                                                          const float* __restrict__ g, const float* __restrict__ be,
+                                                          float* __restrict__ w_out, float* __restrict__ e_out) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;                               // no barrier in this kernel
+  const long b = row / T;
+  const int t = (int)(row % T);
+  tas_encoder_row(x + b * x_s + (long)t * (L / 2), row, N, L, ew, eb, g, be, w_out, e_out);
+}
+
+// Ragged: frame t of utterance b covers samples [t L/2, t L/2 + L) of its row, all below S_out_b <= S_b.
+__global__ __launch_bounds__(256) void tas_encoder_ragged_kernel(const float* __restrict__ x, long x_s, Rag rg, int N, int L,
+                                                                 const float* __restrict__ ew, const float* __restrict__ eb,
+                                                                 const float* __restrict__ g, const float* __restrict__ be,
+                                                                 float* __restrict__ w_out, float* __restrict__ e_out) {
+  const int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (row >= rg.row[rg.n]) return;                    // no barrier in this kernel
+  const int b = rag_find(rg.row, rg.n, row);
+  const int t = row - rg.row[b];
+  tas_encoder_row(x + (long)b * x_s + (long)t * (L / 2), row, N, L, ew, eb, g, be, w_out, e_out);
+}
+
 // ---- PReLU_1 + statistics of norm_1 -----------------------------------------------------------------------------------------
 // grid (chunks of 64 frames, utterances); each wave takes every 4th frame of the chunk.
 //   gLN: fp64 (sum, sum of squares) of the chunk -> part[(b * nch + chunk) * 2 + {0, 1}] (fixed order: lanes, then waves)
 //   cLN: per frame (mean, rstd) -> rstat[row * 2 + {0, 1}] (two passes over the row, as LayerNorm)
 // SAVE (training forward): the pre-PReLU values are read from `src` and stay there; c receives PReLU(src).
+// One chunk: frames [t0, t1) of the utterance whose rows start at `base`; part2 = this chunk's (sum, sum of squares) pair.
 template <bool SAVE>
-__global__ __launch_bounds__(256) void tas_prelu_stats_kernel(float* __restrict__ c, int T, int H, const float* __restrict__ alpha,
-                                                              int norm, double* __restrict__ part, float* __restrict__ rstat,
-                                                              const float* __restrict__ src) {
+__device__ __forceinline__ void tas_prelu_stats_chunk(float* __restrict__ c, long base, int t0, int t1, int H,
+                                                      const float* __restrict__ alpha, int norm, double* __restrict__ part2,
+                                                      float* __restrict__ rstat, const float* __restrict__ src) {
   __shared__ double red[4][2];
   const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int b = blockIdx.y, nch = gridDim.x;
-  const int t0 = blockIdx.x * ROWS_PER_CHUNK, t1 = t0 + ROWS_PER_CHUNK < T ? t0 + ROWS_PER_CHUNK : T;
   const float a = alpha[0];
   double s = 0.0, q = 0.0;
   for (int t = t0 + wv; t < t1; t += 4) {
-    float* r = c + ((long)b * T + t) * H;
+    float* r = c + (base + t) * H;
     float rs = 0.0f;
     for (int k = ln; k < H; k += 64) {
-      float v = SAVE ? src[((long)b * T + t) * H + k] : r[k];
+      float v = SAVE ? src[(base + t) * H + k] : r[k];
       v = v >= 0.0f ? v : a * v;
       r[k] = v;
       if (norm == ONSSEN_TASNET_GLN) { s += (double)v; q += (double)v * (double)v; }
@@ -217,8 +261,8 @@ __global__ __launch_bounds__(256) void tas_prelu_stats_kernel(float* __restrict_
       for (int k = ln; k < H; k += 64) rq += (r[k] - mean) * (r[k] - mean);
       const float var = wave_sum(rq) / (float)H;
       if (ln == 0) {
-        rstat[((long)b * T + t) * 2] = mean;
-        rstat[((long)b * T + t) * 2 + 1] = 1.0f / sqrtf(var + EPS);
+        rstat[(base + t) * 2] = mean;
+        rstat[(base + t) * 2 + 1] = 1.0f / sqrtf(var + EPS);
       }
     }
   }
@@ -229,26 +273,47 @@ __global__ __launch_bounds__(256) void tas_prelu_stats_kernel(float* __restrict_
   }
   __syncthreads();
   if (norm == ONSSEN_TASNET_GLN && threadIdx.x == 0) {
-    part[((long)b * nch + blockIdx.x) * 2] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-    part[((long)b * nch + blockIdx.x) * 2 + 1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+    part2[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+    part2[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
   }
+}
+
+template <bool SAVE>
+__global__ __launch_bounds__(256) void tas_prelu_stats_kernel(float* __restrict__ c, int T, int H, const float* __restrict__ alpha,
+                                                              int norm, double* __restrict__ part, float* __restrict__ rstat,
+                                                              const float* __restrict__ src) {
+  const int b = blockIdx.y, nch = gridDim.x;
+  const int t0 = blockIdx.x * ROWS_PER_CHUNK, t1 = t0 + ROWS_PER_CHUNK < T ? t0 + ROWS_PER_CHUNK : T;
+  tas_prelu_stats_chunk<SAVE>(c, (long)b * T, t0, t1, H, alpha, norm, part + ((long)b * nch + blockIdx.x) * 2, rstat, src);
+}
+
+// Ragged: grid = all chunks of all utterances; chunks are counted from the utterance's own frame 0, and the partial sums of
+// utterance b lie at part[2 blk[b] ...] in chunk order -- the partition and the merge order of the one-utterance run.
+__global__ __launch_bounds__(256) void tas_prelu_stats_ragged_kernel(float* __restrict__ c, Rag rg, int H,
+                                                                     const float* __restrict__ alpha, int norm,
+                                                                     double* __restrict__ part, float* __restrict__ rstat) {
+  const int b = rag_find(rg.blk, rg.n, (int)blockIdx.x);
+  const int T = rg.row[b + 1] - rg.row[b];
+  const int t0 = ((int)blockIdx.x - rg.blk[b]) * ROWS_PER_CHUNK, t1 = t0 + ROWS_PER_CHUNK < T ? t0 + ROWS_PER_CHUNK : T;
+  tas_prelu_stats_chunk<false>(c, (long)rg.row[b], t0, t1, H, alpha, norm, part + (long)blockIdx.x * 2, rstat, nullptr);
 }
 
 // ---- K2: norm_1 on load + dilated depthwise convolution ----------------------------------------------------------------------
 // grid (chunks of 32 frames, utterances); threads over channels.  Output frame t reads normalised frames t + d p - pad_l,
 // zeros outside [0, T).
-__global__ __launch_bounds__(256) void tas_dwconv_kernel(const float* __restrict__ c, int T, int H, int P, int dil, int pad_l,
-                                                         int norm, const double* __restrict__ part, int nch,
-                                                         const float* __restrict__ rstat, const float* __restrict__ na,
-                                                         const float* __restrict__ nb, const float* __restrict__ dw,
-                                                         const float* __restrict__ dwb, float* __restrict__ out) {
+// One tile: output frames [t0, t0 + DW_ROWS) of the utterance of T frames whose rows start at `base`; part = that utterance's
+// nch gLN partial pairs.
+__device__ __forceinline__ void tas_dwconv_tile(const float* __restrict__ c, long base, int T, int t0, int H, int P, int dil,
+                                                int pad_l, int norm, const double* __restrict__ part, int nch,
+                                                const float* __restrict__ rstat, const float* __restrict__ na,
+                                                const float* __restrict__ nb, const float* __restrict__ dw,
+                                                const float* __restrict__ dwb, float* __restrict__ out) {
   __shared__ float gstat[2];
-  const int b = blockIdx.y;
   if (threadIdx.x == 0) {
     float mean = 0.0f, rstd = 1.0f;
     if (norm == ONSSEN_TASNET_GLN) {
       double s = 0.0, q = 0.0;
-      for (int i = 0; i < nch; ++i) { s += part[((long)b * nch + i) * 2]; q += part[((long)b * nch + i) * 2 + 1]; }
+      for (int i = 0; i < nch; ++i) { s += part[(long)i * 2]; q += part[(long)i * 2 + 1]; }
       const double cnt = (double)T * H, m = s / cnt;
       double var = q / cnt - m * m;
       var = var > 0.0 ? var : 0.0;
@@ -260,8 +325,7 @@ __global__ __launch_bounds__(256) void tas_dwconv_kernel(const float* __restrict
   }
   __syncthreads();
   const float gmean = gstat[0], grstd = gstat[1];
-  const int t0 = blockIdx.x * DW_ROWS, t1 = t0 + DW_ROWS < T ? t0 + DW_ROWS : T;
-  const long base = (long)b * T;
+  const int t1 = t0 + DW_ROWS < T ? t0 + DW_ROWS : T;
   for (int k = threadIdx.x; k < H; k += blockDim.x) {
     const float ga = na[k], gb = nb[k], bias = dwb[k];
     for (int t = t0; t < t1; ++t) {
@@ -279,6 +343,30 @@ __global__ __launch_bounds__(256) void tas_dwconv_kernel(const float* __restrict
       out[(base + t) * H + k] = acc;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void tas_dwconv_kernel(const float* __restrict__ c, int T, int H, int P, int dil, int pad_l,
+                                                         int norm, const double* __restrict__ part, int nch,
+                                                         const float* __restrict__ rstat, const float* __restrict__ na,
+                                                         const float* __restrict__ nb, const float* __restrict__ dw,
+                                                         const float* __restrict__ dwb, float* __restrict__ out) {
+  const int b = blockIdx.y;
+  tas_dwconv_tile(c, (long)b * T, T, blockIdx.x * DW_ROWS, H, P, dil, pad_l, norm, part + (long)b * nch * 2, nch, rstat, na, nb, dw,
+                  dwb, out);
+}
+
+// Ragged: grid = all 32-frame tiles of all utterances.  A tap outside [0, T_b) of the OWN utterance is zero padding (it never
+// reads a neighbour's rows); cs[b] = first gLN chunk of utterance b (the statistics kernel's blk table).
+struct RagChunks { int at[MAX_UTT + 1]; };
+__global__ __launch_bounds__(256) void tas_dwconv_ragged_kernel(const float* __restrict__ c, Rag rg, RagChunks cs, int H, int P,
+                                                                int dil, int pad_l, int norm, const double* __restrict__ part,
+                                                                const float* __restrict__ rstat, const float* __restrict__ na,
+                                                                const float* __restrict__ nb, const float* __restrict__ dw,
+                                                                const float* __restrict__ dwb, float* __restrict__ out) {
+  const int b = rag_find(rg.blk, rg.n, (int)blockIdx.x);
+  const int T = rg.row[b + 1] - rg.row[b];
+  tas_dwconv_tile(c, (long)rg.row[b], T, ((int)blockIdx.x - rg.blk[b]) * DW_ROWS, H, P, dil, pad_l, norm,
+                  part + (long)cs.at[b] * 2, cs.at[b + 1] - cs.at[b], rstat, na, nb, dw, dwb, out);
 }
 
 __global__ __launch_bounds__(256) void tas_residual_kernel(float* __restrict__ x, const float* __restrict__ y, long n) {
@@ -316,18 +404,19 @@ __global__ __launch_bounds__(256) void tas_mask_kernel(float* __restrict__ m, co
 // grid (chunks of 16 hop-sized output blocks, utterances, speakers).  Output block j (samples [j hop, (j + 1) hop)) is covered
 // by frames j (first half of its L taps) and j - 1 (second half); there are T + 1 blocks.  The workgroup first contracts the 17
 // frames it needs over the N channels into LDS, then every output sample is written by exactly one thread.
-__global__ __launch_bounds__(256) void tas_decoder_kernel(const float* __restrict__ d, int T, int N, int L, int spk,
-                                                          const float* __restrict__ dw, const float* __restrict__ db,
-                                                          float* __restrict__ out, int S_out) {
+// One tile: output blocks [j0, j0 + DEC_FRAMES) of speaker s of the utterance of T frames whose rows start at `base`; o = that
+// (speaker, utterance)'s output row of S_out valid samples.
+__device__ __forceinline__ void tas_decoder_tile(const float* __restrict__ d, long base, int T, int j0, int s, int N, int L,
+                                                 int spk, const float* __restrict__ dw, const float* __restrict__ db,
+                                                 float* __restrict__ o, int S_out) {
   __shared__ float Ps[(DEC_FRAMES + 1) * MAX_L];
-  const int b = blockIdx.y, s = blockIdx.z, n = gridDim.y, hop = L / 2;
-  const int j0 = blockIdx.x * DEC_FRAMES;
+  const int hop = L / 2;
   const long ldd = (long)spk * N;
   for (int e = threadIdx.x; e < (DEC_FRAMES + 1) * L; e += blockDim.x) {
     const int jj = e / L, l = e % L, f = j0 - 1 + jj;
     float acc = 0.0f;
     if (f >= 0 && f < T) {
-      const float* r = d + ((long)b * T + f) * ldd + (long)s * N;
+      const float* r = d + (base + f) * ldd + (long)s * N;
       for (int k = 0; k < N; ++k) acc += r[k] * dw[k * L + l];
     }
     Ps[jj * L + l] = acc;
@@ -335,7 +424,6 @@ __global__ __launch_bounds__(256) void tas_decoder_kernel(const float* __restric
   __syncthreads();
   const float bias = db[0];
   const int i0 = j0 * hop, i1 = (j0 + DEC_FRAMES) * hop < S_out ? (j0 + DEC_FRAMES) * hop : S_out;
-  float* o = out + ((long)s * n + b) * S_out;
   for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
     const int j = i / hop, off = i - j * hop, jj = j - (j0 - 1);
     float v = bias;
@@ -343,6 +431,26 @@ __global__ __launch_bounds__(256) void tas_decoder_kernel(const float* __restric
     if (j >= 1) v += Ps[(jj - 1) * L + off + hop];    // frame j - 1, tap off + hop
     o[i] = v;
   }
+}
+
+__global__ __launch_bounds__(256) void tas_decoder_kernel(const float* __restrict__ d, int T, int N, int L, int spk,
+                                                          const float* __restrict__ dw, const float* __restrict__ db,
+                                                          float* __restrict__ out, int S_out) {
+  const int b = blockIdx.y, s = blockIdx.z, n = gridDim.y;
+  tas_decoder_tile(d, (long)b * T, T, blockIdx.x * DEC_FRAMES, s, N, L, spk, dw, db, out + ((long)s * n + b) * S_out, S_out);
+}
+
+// Ragged: grid (all 16-block tiles of all utterances, speakers); out = spk x n rows of out_stride floats.  The utterance's last
+// tile also writes the zeros of [S_out_b, out_stride), so every float of `out` has exactly one writer.
+__global__ __launch_bounds__(256) void tas_decoder_ragged_kernel(const float* __restrict__ d, Rag rg, int N, int L, int spk,
+                                                                 const float* __restrict__ dw, const float* __restrict__ db,
+                                                                 float* __restrict__ out, long out_stride) {
+  const int b = rag_find(rg.blk, rg.n, (int)blockIdx.x), s = blockIdx.y;
+  const int T = rg.row[b + 1] - rg.row[b], S_out = (T - 1) * (L / 2) + L;
+  float* o = out + ((long)s * rg.n + b) * out_stride;
+  tas_decoder_tile(d, (long)rg.row[b], T, ((int)blockIdx.x - rg.blk[b]) * DEC_FRAMES, s, N, L, spk, dw, db, o, S_out);
+  if ((int)blockIdx.x + 1 == rg.blk[b + 1])
+    for (long i = S_out + threadIdx.x; i < out_stride; i += blockDim.x) o[i] = 0.0f;
 }
 
 static unsigned ew_grid(long total) { const long nb = (total + 255) / 256; return (unsigned)(nb > 16384 ? 16384 : nb < 1 ? 1 : nb); }
@@ -356,6 +464,110 @@ static int gemm(const Cfg& g, int kind, const float* A, long M, int K, const flo
   if (rc) return rc;
   const int mode = ONSSEN_EPI_BIAS | (g.prec == ONSSEN_TASNET_BF16 ? ONSSEN_EPI_BF16 : 0);
   return onssen_linear_x3p(image, (int)M, K, w3, bias, Nout, mode, 0, 0.0f, C, 1, Nout, 0, stream);
+}
+
+// What a forward needs to know about its batch.  Rectangular: n utterances of T frames.  Ragged: the tables of the four
+// boundary-aware kernels (the same row prefix sums, each with its own workgroup prefix sums) built from the host lengths.
+struct Geo {
+  bool ragged;
+  int n, T, S_out;                 // rectangular
+  long M;                          // rows in all
+  long out_stride;                 // ragged: floats per (speaker, utterance) row of out
+  Rag st, dwc, dec;                // ragged: blk = 64-frame chunks / 32-frame tiles / 16-block decoder tiles
+  RagChunks cs;
+};
+
+// false: a length the ragged forward refuses (n out of range, S_b < L, S_b > x_stride, M over the GEMMs' row bound)
+static bool ragged_geo(const Cfg& g, int n, const int32_t* len, int64_t x_stride, Geo* o) {
+  if (n <= 0 || n > MAX_UTT || !len) return false;
+  const int hop = g.L / 2;
+  o->ragged = true;
+  o->n = o->st.n = o->dwc.n = o->dec.n = n;
+  o->T = o->S_out = 0;
+  o->st.row[0] = o->st.blk[0] = o->dwc.blk[0] = o->dec.blk[0] = 0;
+  long M = 0;
+  for (int b = 0; b < n; ++b) {
+    if (len[b] < g.L || (x_stride >= 0 && len[b] > x_stride)) return false;
+    const int T = (len[b] - g.L) / hop + 1, S_out = (T - 1) * hop + g.L;
+    M += T;
+    if (M > 0x7fffffffL / 4) return false;
+    if (S_out > o->S_out) o->S_out = S_out;                   // the longest output: the least out_stride
+    o->st.row[b + 1] = (int)M;
+    o->st.blk[b + 1] = o->st.blk[b] + ceil_div(T, ROWS_PER_CHUNK);
+    o->dwc.blk[b + 1] = o->dwc.blk[b] + ceil_div(T, DW_ROWS);
+    o->dec.blk[b + 1] = o->dec.blk[b] + ceil_div(T + 1, DEC_FRAMES);
+  }
+  for (int b = 0; b <= n; ++b) {
+    o->dwc.row[b] = o->dec.row[b] = o->st.row[b];
+    o->cs.at[b] = o->st.blk[b];
+  }
+  o->M = M;
+  return true;
+}
+
+// The forward over validated arguments: the launches of the rectangular and of the ragged entry differ in four places.
+static int forward(const Cfg& g, const void* image, const float* x, int64_t x_stride, float* out, void* ws, const Ws& w,
+                   const Geo& q, void* stream) {
+  const Layout o = layout(g);
+  ONSSEN_CLEAR_ERROR();
+  hipStream_t st = (hipStream_t)stream;
+  const char* im = static_cast<const char*>(image);
+  char* wb = static_cast<char*>(ws);
+  auto fi = [&](size_t off) { return reinterpret_cast<const float*>(im + off); };
+  auto ui = [&](size_t off) { return reinterpret_cast<const uint16_t*>(im + off); };
+  float *bw = reinterpret_cast<float*>(wb + w.w), *be = reinterpret_cast<float*>(wb + w.e), *bx = reinterpret_cast<float*>(wb + w.x),
+        *bc = reinterpret_cast<float*>(wb + w.c), *bt = reinterpret_cast<float*>(wb + w.t);
+  uint16_t* img = reinterpret_cast<uint16_t*>(wb + w.img);
+  double* part = reinterpret_cast<double*>(wb + w.st);
+  float* rstat = reinterpret_cast<float*>(wb + w.st);
+  const int n = q.n, T = q.T;
+  const long M = q.M;
+  // K1: encoder + LayerN_S, then the bottleneck
+  if (q.ragged)
+    hipLaunchKernelGGL(tas_encoder_ragged_kernel, dim3((unsigned)ceil_div((int)M, 4)), dim3(256), 0, st, x, (long)x_stride, q.st,
+                       g.N, g.L, fi(o.enc_w), fi(o.enc_b), fi(o.ln_g), fi(o.ln_b), bw, be);
+  else
+    hipLaunchKernelGGL(tas_encoder_kernel, dim3((unsigned)ceil_div((int)M, 4)), dim3(256), 0, st, x, (long)x_stride, T, M, g.N,
+                       g.L, fi(o.enc_w), fi(o.enc_b), fi(o.ln_g), fi(o.ln_b), bw, be);
+  ONSSEN_LAUNCH_CHECK();
+  int rc = gemm(g, ONSSEN_TASNET_EXACT_BOTTLENECK, be, M, g.N, fi(o.bott_w), ui(o.bott_x3), fi(o.bott_b), g.B, bx, img, stream);
+  if (rc) return rc;
+  const int nch = ceil_div(T, ROWS_PER_CHUNK);
+  for (int j = 0; j < g.R * g.X; ++j) {
+    const size_t k = o.blk0 + (size_t)j * o.blk_stride, k3 = o.x3_blk0 + (size_t)j * o.x3_blk_stride;
+    const int dil = 1 << (j % g.X);
+    const int pad_l = g.causal ? dil * (g.P - 1) : dil * (g.P - 1) / 2;
+    rc = gemm(g, ONSSEN_TASNET_EXACT_CONV1X1, bx, M, g.B, fi(k + o.c1_w), ui(k3 + o.c1_x3), fi(k + o.c1_b), g.H, bc, img, stream);
+    if (rc) return rc;
+    if (q.ragged) {
+      hipLaunchKernelGGL(tas_prelu_stats_ragged_kernel, dim3((unsigned)q.st.blk[n]), dim3(256), 0, st, bc, q.st, g.H, fi(k + o.alpha),
+                         g.norm, part, rstat);
+      hipLaunchKernelGGL(tas_dwconv_ragged_kernel, dim3((unsigned)q.dwc.blk[n]), dim3(256), 0, st, bc, q.dwc, q.cs, g.H, g.P, dil,
+                         pad_l, g.norm, part, rstat, fi(k + o.n_a), fi(k + o.n_b), fi(k + o.dw_w), fi(k + o.dw_b), be);
+    } else {
+      hipLaunchKernelGGL(tas_prelu_stats_kernel<false>, dim3((unsigned)nch, (unsigned)n), dim3(256), 0, st, bc, T, g.H,
+                         fi(k + o.alpha), g.norm, part, rstat, (const float*)nullptr);
+      hipLaunchKernelGGL(tas_dwconv_kernel, dim3((unsigned)ceil_div(T, DW_ROWS), (unsigned)n), dim3(256), 0, st, bc, T, g.H, g.P, dil,
+                         pad_l, g.norm, part, nch, rstat, fi(k + o.n_a), fi(k + o.n_b), fi(k + o.dw_w), fi(k + o.dw_b), be);
+    }
+    ONSSEN_LAUNCH_CHECK();
+    rc = gemm(g, ONSSEN_TASNET_EXACT_SC_CONV, be, M, g.H, fi(k + o.sc_w), ui(k3 + o.sc_x3), fi(k + o.sc_b), g.B, bt, img, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tas_residual_kernel, dim3(ew_grid(M * g.B)), dim3(256), 0, st, bx, bt, M * g.B);
+    ONSSEN_LAUNCH_CHECK();
+  }
+  rc = gemm(g, ONSSEN_TASNET_EXACT_MASKS, bx, M, g.B, fi(o.mask_w), ui(o.mask_x3), fi(o.mask_b), g.spk * g.N, bt, img, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(tas_mask_kernel<false>, dim3(ew_grid(M * g.N)), dim3(256), 0, st, bt, bw, M, g.N, g.spk, g.act,
+                     (const float*)nullptr);
+  if (q.ragged)
+    hipLaunchKernelGGL(tas_decoder_ragged_kernel, dim3((unsigned)q.dec.blk[n], (unsigned)g.spk), dim3(256), 0, st, bt, q.dec, g.N,
+                       g.L, g.spk, fi(o.dec_w), fi(o.dec_b), out, q.out_stride);
+  else
+    hipLaunchKernelGGL(tas_decoder_kernel, dim3((unsigned)ceil_div(T + 1, DEC_FRAMES), (unsigned)n, (unsigned)g.spk), dim3(256), 0,
+                       st, bt, T, g.N, g.L, g.spk, fi(o.dec_w), fi(o.dec_b), out, q.S_out);
+  ONSSEN_LAUNCH_CHECK();
+  return ONSSEN_OK;
 }
 
 }  // namespace tas
@@ -431,55 +643,36 @@ int onssen_tasnet_forward_f32(const int32_t* cfg_host, const void* image, const 
                               float* out, void* ws, size_t ws_bytes, void* stream) {
   tas::Cfg g;
   if (!tas::read_cfg(cfg_host, &g) || !image || !x || !out || !ws || n <= 0 || S < g.L || x_stride < S) return ONSSEN_E_ARG;
-  const tas::Layout o = tas::layout(g);
   const tas::Ws w = tas::ws_layout(g, n, S);
   if (ws_bytes < w.total) return ONSSEN_E_WORKSPACE;
   if ((reinterpret_cast<uintptr_t>(image) & 255u) != 0 || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0) return ONSSEN_E_ALIGN;
   const int hop = g.L / 2, T = (S - g.L) / hop + 1, S_out = (T - 1) * hop + g.L;
   const long M = (long)n * T;
   if (M > 0x7fffffffL / 4) return ONSSEN_E_ARG;
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  const char* im = static_cast<const char*>(image);
-  char* wb = static_cast<char*>(ws);
-  auto fi = [&](size_t off) { return reinterpret_cast<const float*>(im + off); };
-  auto ui = [&](size_t off) { return reinterpret_cast<const uint16_t*>(im + off); };
-  float *bw = reinterpret_cast<float*>(wb + w.w), *be = reinterpret_cast<float*>(wb + w.e), *bx = reinterpret_cast<float*>(wb + w.x),
-        *bc = reinterpret_cast<float*>(wb + w.c), *bt = reinterpret_cast<float*>(wb + w.t);
-  uint16_t* img = reinterpret_cast<uint16_t*>(wb + w.img);
-  double* part = reinterpret_cast<double*>(wb + w.st);
-  float* rstat = reinterpret_cast<float*>(wb + w.st);
-  // K1: encoder + LayerN_S, then the bottleneck
-  hipLaunchKernelGGL(tas::tas_encoder_kernel, dim3((unsigned)ceil_div((int)M, 4)), dim3(256), 0, st, x, (long)x_stride, T, M, g.N,
-                     g.L, fi(o.enc_w), fi(o.enc_b), fi(o.ln_g), fi(o.ln_b), bw, be);
-  ONSSEN_LAUNCH_CHECK();
-  int rc = tas::gemm(g, ONSSEN_TASNET_EXACT_BOTTLENECK, be, M, g.N, fi(o.bott_w), ui(o.bott_x3), fi(o.bott_b), g.B, bx, img, stream);
-  if (rc) return rc;
-  const int nch = ceil_div(T, tas::ROWS_PER_CHUNK);
-  for (int j = 0; j < g.R * g.X; ++j) {
-    const size_t k = o.blk0 + (size_t)j * o.blk_stride, k3 = o.x3_blk0 + (size_t)j * o.x3_blk_stride;
-    const int dil = 1 << (j % g.X);
-    const int pad_l = g.causal ? dil * (g.P - 1) : dil * (g.P - 1) / 2;
-    rc = tas::gemm(g, ONSSEN_TASNET_EXACT_CONV1X1, bx, M, g.B, fi(k + o.c1_w), ui(k3 + o.c1_x3), fi(k + o.c1_b), g.H, bc, img, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tas::tas_prelu_stats_kernel<false>, dim3((unsigned)nch, (unsigned)n), dim3(256), 0, st, bc, T, g.H,
-                       fi(k + o.alpha), g.norm, part, rstat, (const float*)nullptr);
-    hipLaunchKernelGGL(tas::tas_dwconv_kernel, dim3((unsigned)ceil_div(T, tas::DW_ROWS), (unsigned)n), dim3(256), 0, st, bc, T, g.H,
-                       g.P, dil, pad_l, g.norm, part, nch, rstat, fi(k + o.n_a), fi(k + o.n_b), fi(k + o.dw_w), fi(k + o.dw_b), be);
-    ONSSEN_LAUNCH_CHECK();
-    rc = tas::gemm(g, ONSSEN_TASNET_EXACT_SC_CONV, be, M, g.H, fi(k + o.sc_w), ui(k3 + o.sc_x3), fi(k + o.sc_b), g.B, bt, img, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tas::tas_residual_kernel, dim3(tas::ew_grid(M * g.B)), dim3(256), 0, st, bx, bt, M * g.B);
-    ONSSEN_LAUNCH_CHECK();
-  }
-  rc = tas::gemm(g, ONSSEN_TASNET_EXACT_MASKS, bx, M, g.B, fi(o.mask_w), ui(o.mask_x3), fi(o.mask_b), g.spk * g.N, bt, img, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(tas::tas_mask_kernel<false>, dim3(tas::ew_grid(M * g.N)), dim3(256), 0, st, bt, bw, M, g.N, g.spk, g.act,
-                     (const float*)nullptr);
-  hipLaunchKernelGGL(tas::tas_decoder_kernel, dim3((unsigned)ceil_div(T + 1, tas::DEC_FRAMES), (unsigned)n, (unsigned)g.spk),
-                     dim3(256), 0, st, bt, T, g.N, g.L, g.spk, fi(o.dec_w), fi(o.dec_b), out, S_out);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
+  tas::Geo q{};
+  q.ragged = false; q.n = n; q.T = T; q.S_out = S_out; q.M = M;
+  return tas::forward(g, image, x, x_stride, out, ws, w, q, stream);
+}
+
+size_t onssen_tasnet_ragged_workspace_bytes(const int32_t* cfg_host, int n, const int32_t* lengths_host) {
+  tas::Cfg g;
+  tas::Geo q{};
+  if (!tas::read_cfg(cfg_host, &g) || !tas::ragged_geo(g, n, lengths_host, -1, &q)) return 0;
+  return tas::ws_layout_rows(g, (size_t)q.M, (size_t)q.st.blk[n]).total;
+}
+
+int onssen_tasnet_forward_ragged_f32(const int32_t* cfg_host, const void* image, const float* x, int n,
+                                     const int32_t* lengths_host, int64_t x_stride, float* out, int64_t out_stride, void* ws,
+                                     size_t ws_bytes, void* stream) {
+  tas::Cfg g;
+  tas::Geo q{};
+  if (!tas::read_cfg(cfg_host, &g) || !image || !x || !out || !ws || x_stride < 0) return ONSSEN_E_ARG;
+  if (!tas::ragged_geo(g, n, lengths_host, x_stride, &q) || out_stride < q.S_out) return ONSSEN_E_ARG;
+  const tas::Ws w = tas::ws_layout_rows(g, (size_t)q.M, (size_t)q.st.blk[n]);
+  if (ws_bytes < w.total) return ONSSEN_E_WORKSPACE;
+  if ((reinterpret_cast<uintptr_t>(image) & 255u) != 0 || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0) return ONSSEN_E_ALIGN;
+  q.out_stride = out_stride;
+  return tas::forward(g, image, x, x_stride, out, ws, w, q, stream);
 }
 
 }  // extern "C"

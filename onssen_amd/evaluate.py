@@ -324,18 +324,29 @@ class tester_chimera(tester):
 
 class tester_tasnet(tester):
     """egs/wsj0-2mix/tasnet/evaluate.py:11-29: the loader yields ``[mix (1, S')]``, ``[sig_ref (1, C, S')]`` per utterance and
-    ConvTasNet's outputs are the estimates, cut to the reference's length.  ``eval()`` returns the mean SI-SDR.  Only the
-    reference's loop (``batch=1``) is supported: gLN normalises over every frame of a row, so a zero-padded row of a ragged
-    batch would not give the per-utterance result."""
+    ConvTasNet's outputs are the estimates, cut to the reference's length.  ``eval()`` returns the mean SI-SDR.  ``batch=1``
+    (the default) is the reference's loop; ``batch=K`` > 1 evaluates K whole utterances of different lengths per forward
+    (``ConvTasNet.forward(..., lengths=)``: compact rows, each utterance normalised, padded and overlap-added over its own
+    frames), every utterance's SI-SDR bit for bit the batch-1 loop's.  K is at most ``ConvTasNet.RAGGED_MAX``."""
+
+    @staticmethod
+    def collate(items):
+        """``tester.collate`` with the rows' sample counts ALSO as host integers (they are the shapes of the items; the model
+        takes them as kernel arguments): ragged = (host lengths, device lengths)."""
+        inp, lab, (_, lengths) = tester.collate(items)
+        host = [int(i[0].shape[1]) for i, _ in items for _ in range(i[0].shape[0])]
+        return inp, lab, (host, lengths)
+
+    def _one(self, input, label, ragged):
+        if ragged is None:
+            return super()._one(input, label, None)
+        host, lengths = ragged
+        output = self.model(input, lengths=host)
+        sig_est, sig_ref = self.get_est_sig(input, label, output)
+        return batch_SDR_torch(sig_est, sig_ref, lengths=lengths)
 
     def get_est_sig(self, input, label, output):
         sig_ref, = label
         batch, num_spk, n = sig_ref.shape           # estimates cut to the reference's length (S_out >= n)
         sig_est = torch.stack([output[i][..., :n].reshape(batch, n) for i in range(num_spk)], dim=1).float()
         return sig_est, sig_ref
-
-    def eval(self, window=8, batch=1, bucket=1):
-        if int(batch) > 1:
-            raise NotImplementedError("tester_tasnet: batch > 1 is not supported -- gLN over a zero-padded row is not the "
-                                      "per-utterance result; evaluate one utterance per forward (batch=1)")
-        return super().eval(window=window, batch=1, bucket=1)

@@ -165,6 +165,17 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
     forward([x]) with x (S,) or (n, S) -> list of ``num_spks`` tensors, each torch.squeeze-d as upstream: (S_out,) for n = 1,
     (n, S_out) otherwise; T = (S - L) // (L/2) + 1 frames, S_out = (T - 1) L/2 + L (trailing samples are dropped).
 
+    forward([x], lengths=...) (extension, eval only): a RAGGED batch of whole utterances -- x (n, S_max) zero-padded (what lies
+    beyond a row's own length is never read), ``lengths`` a sequence of n ints or a CPU integer tensor, n <= RAGGED_MAX.
+    Returns ``num_spks`` tensors (n, S_out_max), never squeezed; row b holds the estimate of utterance b in [0, S_out_b) and
+    zeros after it, bit for bit what ``forward([x[b, :lengths[b]]])`` returns (gLN statistics, the depthwise convolution's
+    padding and the overlap-add use the utterance's own frames; the activations are compact rows, so a batch costs what its
+    frames cost).  The lengths are kernel arguments, not device data: a device tensor is refused (reading it would stall the
+    stream), and a captured graph is tied to the lengths it was captured with.  Workspace: one grow-only buffer per model
+    (the largest batch seen, times 1.25 at most), so a loop over batches of ever different lengths allocates a handful of
+    times and then never; under graph capture a buffer per tuple of lengths instead (a regrowth must not free memory a
+    captured graph points into).
+
     In eval mode without autograd, on ROCm tensors: the HIP forward (csrc/tasnet.inc) -- the encoder + LayerNorm, every 1x1
     convolution as a row GEMM (exact fp32 under ``precision`` f32 and bf16x3, plain bf16 products under the opt-in bf16: see
     EXACT_KINDS), PReLU + norm statistics, the normalised
@@ -227,6 +238,7 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
     # brings it back with margin (every kind contributes about equally: profiles/tasnet_exact_probe.jsonl); exact fp32 costs 12 %
     # of the forward there (the narrow GEMMs are not what bounds it).  bf16 (opt-in, bf16-grade) keeps plain bf16 products.
     EXACT_KINDS = {"f32": 0, "bf16x3": 15, "bf16": 0}
+    RAGGED_MAX = _abi.TASNET_RAGGED_MAX       # utterances of one ragged forward (the kernels take their table by value)
 
     def _cfg(self, prec):
         return _abi.Lib.tasnet_cfg(self.N, self.L, self.B, self.H, self.P, self.X, self.R, _NORMS[self.norm], self.num_spks,
@@ -286,6 +298,62 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
         lib.tasnet_forward(cfg, image.data_ptr(), x.data_ptr(), n, S, x_stride, out.data_ptr(), ws.data_ptr(), nb, _stream())
         return [torch.squeeze(out[s]) for s in range(self.num_spks)]
 
+    def _ragged_lengths(self, x, lengths):
+        """``lengths`` of a ragged forward of x (n, S_max) as a list of host ints, validated."""
+        if torch.is_tensor(lengths):
+            if lengths.is_cuda:
+                raise TypeError("ConvTasNet: lengths must be host integers (a sequence or a CPU tensor): they size the launches "
+                                "and travel as kernel arguments, so a device tensor would force a synchronisation per forward")
+            if lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+                raise TypeError(f"ConvTasNet: lengths must be an integer tensor, got {lengths.dtype}")
+            lengths = lengths.reshape(-1).tolist()
+        lengths = list(lengths)
+        if any(isinstance(v, bool) or int(v) != v for v in lengths):
+            raise TypeError(f"ConvTasNet: lengths must be integers, got {lengths!r}")
+        lengths = [int(v) for v in lengths]
+        n, S = x.shape
+        if len(lengths) != n:
+            raise ValueError(f"ConvTasNet: {len(lengths)} lengths for a batch of {n} rows")
+        if n > self.RAGGED_MAX:
+            raise ValueError(f"ConvTasNet: a ragged forward takes at most {self.RAGGED_MAX} utterances, got {n} "
+                             "(separation.separate_tasnet splits a longer list)")
+        for b, v in enumerate(lengths):
+            if v < self.L:
+                raise ValueError(f"ConvTasNet: lengths[{b}] = {v} samples is shorter than one encoder frame (L = {self.L})")
+            if v > S:
+                raise ValueError(f"ConvTasNet: lengths[{b}] = {v} exceeds the {S} samples of a row of the input")
+        return lengths
+
+    def _hip_forward_ragged(self, x, lengths):
+        if self.training or not use_hip_path(self) or needs_graph(x):
+            raise RuntimeError("ConvTasNet: lengths= (a ragged batch of whole utterances) is an inference call: it needs eval "
+                               "mode and no autograd (torch.no_grad(), or frozen parameters); training uses fixed-size chunks")
+        why = self.hip_limits()
+        if why:
+            raise RuntimeError("ConvTasNet: the HIP forward cannot run this configuration: " + "; ".join(why))
+        lengths = self._ragged_lengths(x, lengths)
+        require_device(x, "ConvTasNet")
+        n, S = x.shape
+        lib = get_lib()
+        cfg = self._cfg(precision())
+        image = self._get_image(cfg)
+        x = x.float()
+        if x.stride(1) != 1 or (n > 1 and x.stride(0) < S):
+            x = x.contiguous()
+        x_stride = x.stride(0) if n > 1 else S
+        hop = self.L // 2
+        S_out = max((v - self.L) // hop for v in lengths) * hop + self.L
+        ln = lib.tasnet_lengths(lengths)
+        nb = lib.tasnet_ragged_workspace_bytes(cfg, n, ln)
+        if torch.cuda.is_current_stream_capturing():
+            ws = self._ws.get(("tasnet_ragged", str(x.device), tuple(lengths)), nb, x.device)
+        else:
+            ws = self._ws.scratch("tasnet_ragged", nb, 0, x.device)
+        out = torch.empty(self.num_spks, n, S_out, device=x.device, dtype=torch.float32)
+        lib.tasnet_forward_ragged(cfg, image.data_ptr(), x.data_ptr(), n, ln, x_stride, out.data_ptr(), S_out, ws.data_ptr(),
+                                  ws.numel(), _stream())
+        return [out[s] for s in range(self.num_spks)]
+
     def hip_train_limits(self, x=None):
         """Reasons a training forward (of ``x``, if given) cannot run on the HIP training kernels (empty: it can)."""
         why = self.hip_limits()
@@ -308,12 +376,14 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
         return [torch.squeeze(out[s]) for s in range(self.num_spks)]
 
     # ---- forward ------------------------------------------------------------------------------------------------------
-    def forward(self, input):
+    def forward(self, input, lengths=None):
         x, = input
         if x.dim() >= 3:
             raise RuntimeError(f"ConvTasNet accepts 1/2D tensors as input, but got {x.dim()}D")
         if x.dim() == 1:
             x = torch.unsqueeze(x, 0)
+        if lengths is not None:
+            return self._hip_forward_ragged(x, lengths)
         if use_hip_path(self) and not needs_graph(x):
             return self._hip_forward(x)
         if (options.get("tasnet_train") == "hip" and x.is_cuda and all(p.dtype == torch.float32 for p in self._packed_params())

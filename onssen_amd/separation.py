@@ -33,6 +33,28 @@ def separate_chimera(model, wav, window_size=256, hop_size=64, lengths=None):
     return out
 
 
+@torch.no_grad()
+def separate_tasnet(model, waves):
+    """Time-domain separation of whole utterances: ``waves`` a list of 1-D waveforms of any lengths (one device) -> a list of
+    (num_spks, S_out_k) tensors, S_out_k = min(S_k, (T_k - 1) L/2 + L) as ``tester_tasnet`` cuts them (trailing samples that
+    fill no encoder frame are dropped).  The utterances go through ``ConvTasNet.forward(..., lengths=)`` in the order given,
+    ``model.RAGGED_MAX`` per forward; each result is bit for bit the one-utterance forward's."""
+    from torch.nn.utils.rnn import pad_sequence
+    K = int(model.RAGGED_MAX)
+    waves = list(waves)
+    if any(w.dim() != 1 for w in waves):
+        raise ValueError("separate_tasnet: every waveform must be 1-D (samples,)")
+    hop, out = model.L // 2, []
+    for at in range(0, len(waves), K):
+        chunk = waves[at:at + K]
+        lens = [int(w.shape[0]) for w in chunk]
+        est = model([pad_sequence(chunk, batch_first=True)], lengths=lens)
+        for b, S in enumerate(lens):
+            S_out = min(S, ((S - model.L) // hop) * hop + model.L)
+            out.append(torch.stack([e[b, :S_out] for e in est]))
+    return out
+
+
 _CLUSTER_WS = {}           # (device, B, T, F, D[, "compact"], stream) -> buffer of a uniform shape
 _CLUSTER_SCRATCH = {}      # (device, stream) -> grow-only buffer of the ragged / shape-changing calls (see dc_masks)
 _CLUSTER_PINNED = set()    # keys of _CLUSTER_WS handed out for / during a hipGraph capture: never evicted

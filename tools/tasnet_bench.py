@@ -10,7 +10,16 @@ shape is checked on its first 2 utterances).  Usage: python tools/tasnet_bench.p
 warmed up, median and min-max of --reps device-event timed steps each, plus forward-only (network + loss) and backward-only
 splits.  One JSON line per shape (default --out with --train: profiles/tasnet_train_bench.jsonl).
 --train-profile N: N HIP training steps at the recipe shape and nothing else -- the run to put under
-``rocprofv3 --kernel-trace --stats`` (a run of its own: profiling perturbs the timing)."""
+``rocprofv3 --kernel-trace --stats`` (a run of its own: profiling perturbs the timing).
+
+--ragged K[,K...]: whole-utterance evaluation.  64 utterances with seeded lengths uniform in 2 s .. 10 s at 8 kHz, recipe model,
+one pass = the eager forwards of all 64: (a) one utterance per forward (the batch-1 loop), (b) ``forward(..., lengths=)`` with K
+utterances per forward, for every K given (at most ConvTasNet.RAGGED_MAX) and every read-ahead factor of --buckets (G = 1: the
+utterances as they come; G > 1: G K read ahead and sorted by length, as tester.eval does).  The batches are collated before the
+clock starts; the legs are interleaved pass by pass in one process, warmed up, --reps device-event timed passes each.  One JSON
+line per leg: ms per utterance, median / min / max (default --out: profiles/tasnet_ragged_bench.jsonl).  The first pass also
+checks every ragged leg's estimates against the batch-1 leg's, bit for bit.
+--ragged-profile K: 3 passes of the K-per-forward leg and nothing else (the run for ``rocprofv3 --kernel-trace --stats``)."""
 import argparse
 import json
 import os
@@ -153,8 +162,98 @@ def train_leg(a):
             f.write(json.dumps(r) + "\n")
 
 
+def ragged_lengths(count=64, seed=7, lo=16000, hi=80000):
+    return [int(v) for v in np.random.default_rng(seed).integers(lo, hi + 1, count)]
+
+
+def ragged_batches(waves, K, G):
+    """Lists of indices, K per forward; G > 1: G K read ahead, longest first (tester._forwards)."""
+    out = []
+    for at in range(0, len(waves), K * G):
+        idx = list(range(at, min(at + K * G, len(waves))))
+        if G > 1:
+            idx.sort(key=lambda i: -waves[i].shape[0])
+        out += [idx[j:j + K] for j in range(0, len(idx), K)]
+    return out
+
+
+def ragged_leg(a):
+    from torch.nn.utils.rnn import pad_sequence
+    dev = torch.device("cuda:0")
+    c = tasnet_ref.RECIPE
+    sd = tasnet_ref.make_state(c, seed=11)
+    m = onn.ConvTasNet(**c)
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    m = m.to(dev).eval()
+    lens = ragged_lengths()
+    rng = np.random.default_rng(8)
+    waves = [torch.from_numpy((0.1 * rng.standard_normal(s)).astype(np.float32)).to(dev) for s in lens]
+
+    def leg_ragged(K, G):
+        plan = [(pad_sequence([waves[i] for i in idx], batch_first=True), [lens[i] for i in idx], idx)
+                for idx in ragged_batches(waves, K, G)]
+
+        def run(keep=None):
+            for x, ln, idx in plan:
+                est = m([x], lengths=ln)
+                if keep is not None:
+                    for b, i in enumerate(idx):
+                        keep[i] = torch.stack([e[b] for e in est])
+        return run
+
+    def leg_one(keep=None):
+        for i, w in enumerate(waves):
+            est = m([w])
+            if keep is not None:
+                keep[i] = torch.stack(list(est))
+
+    if a.ragged_profile:
+        run = leg_ragged(a.ragged_profile, 1)
+        with torch.no_grad():
+            for _ in range(3):
+                run()
+        torch.cuda.synchronize()
+        return
+    Ks = [int(v) for v in a.ragged.split(",")]
+    Gs = [int(v) for v in a.buckets.split(",")]
+    legs = {"batch1": leg_one}
+    for K in Ks:
+        for G in Gs:
+            legs[f"ragged_K{K}_G{G}"] = leg_ragged(K, G)
+    ts = {name: [] for name in legs}
+    with torch.no_grad():
+        base = {}
+        leg_one(base)
+        for name, run in legs.items():                       # same bits as the batch-1 loop, checked before anything is timed
+            if name == "batch1":
+                continue
+            got = {}
+            run(got)
+            for i, e in base.items():
+                assert torch.equal(got[i][:, :e.shape[1]], e), f"{name}: utterance {i} differs from its one-utterance forward"
+        del base, got
+        for it in range(a.warmup + a.reps):                   # interleaved: every leg once per round
+            for name, run in legs.items():
+                ms, _ = _timed(run)
+                if it >= a.warmup:
+                    ts[name].append(ms / len(waves))
+    lines = []
+    for name in legs:
+        rec = {"leg": name, "utterances": len(waves), "audio_s": sum(lens) / 8000.0, "reps": a.reps, "warmup": a.warmup,
+               "precision": os.environ.get("ONSSEN_PRECISION", "bf16x3"), "ms_per_utterance": _stats(ts[name])}
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+    out = a.out or os.path.join(ROOT, "profiles", "tasnet_ragged_bench.jsonl")
+    with open(out, "w") as f:
+        for r in lines:
+            f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ragged", default=None, metavar="K[,K...]")
+    ap.add_argument("--buckets", default="1,4")
+    ap.add_argument("--ragged-profile", type=int, default=0, metavar="K")
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--train-profile", type=int, default=0)
     ap.add_argument("--warmup", type=int, default=3)
@@ -162,6 +261,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--shapes", default=None)
     a = ap.parse_args()
+    if a.ragged or a.ragged_profile:
+        return ragged_leg(a)
     if a.train or a.train_profile:
         a.shapes = a.shapes or "3x32000,16x32000"
         return train_leg(a)
