@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ONSSEN_ABI_VERSION 14   /* 14 (additions, no signature changed): onssen_tasnet_forward_ragged_f32 and onssen_tasnet_ragged_workspace_bytes (Conv-TasNet over whole utterances of different lengths).  14 (additions, no signature changed): onssen_tasnet_train_forward_f32, onssen_tasnet_backward_f32 and their two size queries (Conv-TasNet training).  14 (additions, no signature changed): onssen_tasnet_* (the Conv-TasNet separation forward).  14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
+#define ONSSEN_ABI_VERSION 14   /* 14 (additions, no signature changed): onssen_tasnet_stream_* (stateful streaming inference of causal Conv-TasNet models).  14 (additions, no signature changed): onssen_tasnet_forward_ragged_f32 and onssen_tasnet_ragged_workspace_bytes (Conv-TasNet over whole utterances of different lengths).  14 (additions, no signature changed): onssen_tasnet_train_forward_f32, onssen_tasnet_backward_f32 and their two size queries (Conv-TasNet training).  14 (additions, no signature changed): onssen_tasnet_* (the Conv-TasNet separation forward).  14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
 
 #define ONSSEN_OK 0
 #define ONSSEN_E_ARG (-1)         /* invalid argument / unsupported shape */
@@ -771,6 +771,50 @@ size_t onssen_tasnet_backward_workspace_bytes(const int32_t* cfg_host, int n, in
 int onssen_tasnet_backward_f32(const int32_t* cfg_host, const void* image, const float* x, int n, int S, int64_t x_stride,
                                const void* saved, size_t saved_bytes, const float* d_out, float* d_params, void* ws, size_t ws_bytes,
                                void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Conv-TasNet STREAMING inference: n concurrent streams of a causal model that advance in lockstep, all state on the device.
+ * cfg / image as above.  Only causal = 1 with norm = CLN or BN can stream (gLN statistics span the utterance, a non-causal block
+ * looks ahead), and the deepest block's history (P - 1) 2^(X - 1) must not exceed ONSSEN_TASNET_STREAM_MAX_HISTORY frames: any
+ * other configuration gets ONSSEN_E_ARG (size queries: 0) and nothing is launched.  hop = L/2.
+ * step: x_new = n rows of frames * hop NEW samples (row stride x_stride >= frames * hop floats); out = num_spks x n x
+ *   (frames * hop), contiguous.  frames >= 1 may differ from call to call.  ws = onssen_tasnet_stream_workspace_bytes(cfg, n,
+ *   frames) bytes, 256-byte aligned, no zeroing needed, free between steps.
+ * Delay: exactly ONE hop.  A hop of samples completes the frame that began one hop earlier, so after a reset the first hop of
+ *   output is exactly zero, and from there the concatenated step outputs hold the offline output blocks 0, 1, ...: for a stream
+ *   that was reset, fed M hops in steps of any sizes and flushed, concat(steps)[hop:] followed by flush's hop is BIT FOR BIT
+ *   onssen_tasnet_forward_f32 of the whole M * hop samples (S_out = S there), at every precision.  flush = the last block (the
+ *   decoder bias + the second half of the last frame's taps; zeros while the stream holds no complete frame); it changes nothing,
+ *   so the stream may go on.  Taps and overlap-add terms that reach before a stream's frame 0 contribute nothing (skipped, as the
+ *   forward skips them: NOT a zero row through the normalisation).
+ * state: onssen_tasnet_stream_state_bytes(cfg, n) bytes (0: n < 1, n > 65535 or the size overflows), 256-byte aligned, each
+ *   region 256-aligned, in this order:
+ *     int64 next_frame[n]                 index of the next frame of each stream; -1 after reset; advanced by the step itself
+ *     float carry_x[n][hop]               the last hop of samples (first half of the next frame)
+ *     float carry_dec[num_spks][n][hop]   second half of the last frame's decoder taps (before the bias)
+ *     per block j = r * X + x, history = (P - 1) 2^x frames:
+ *       float ring[n][history][H]         conv1x1 + PReLU output of the last `history` frames; frame g in slot (g + 1) mod history
+ *       float stat[n][history][2]         their cLN (mean, rstd) (unused under BN)
+ *   (recipe N 512, H 512, P 3, X 8, R 3: 3 * 510 rows of 512 + 2 floats per stream, 3.1 MB.)
+ *   reset: slots_host = n_slots HOST stream indices in [0, n) (NULL, 0: all); zeroes every byte of those streams' state and sets
+ *   their counters to -1, whatever the buffer held; the other streams are untouched.  A new state buffer must be reset once.
+ * The frame counters live on the device and no argument but the pointers changes from step to step, so ONE captured graph of a
+ *   step serves every later step of the same (n, frames).  No launch writes a state row that another workgroup of the same
+ *   launch reads (the history ring is written by a launch of its own after its readers).  No atomics, no spinning, no
+ *   allocation; ordinary launches on `stream`; two runs give the same bits.
+ * ONSSEN_E_ARG: a configuration that cannot stream, n < 1, frames < 1, n * frames > 2^31 / 4, x_stride < frames * hop, a slot
+ *   outside [0, n).  ONSSEN_E_WORKSPACE: state_bytes or ws_bytes too small.  Both before anything is launched or written. */
+#define ONSSEN_TASNET_STREAM_RESET_MAX 64          /* slots per round of reset launches (internal batching; any n_slots works) */
+#define ONSSEN_TASNET_STREAM_MAX_HISTORY 16777216  /* frames */
+size_t onssen_tasnet_stream_state_bytes(const int32_t* cfg_host, int n);
+int onssen_tasnet_stream_reset(const int32_t* cfg_host, void* state, size_t state_bytes, int n, const int32_t* slots_host,
+                               int n_slots, void* stream);
+size_t onssen_tasnet_stream_workspace_bytes(const int32_t* cfg_host, int n, int frames);
+int onssen_tasnet_stream_step_f32(const int32_t* cfg_host, const void* image, const float* x_new, int n, int frames,
+                                  int64_t x_stride, float* out, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
+                                  void* stream);
+int onssen_tasnet_stream_flush_f32(const int32_t* cfg_host, const void* image, const void* state, size_t state_bytes, int n,
+                                   float* out_tail, void* stream);
 
 #ifdef __cplusplus
 }

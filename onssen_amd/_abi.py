@@ -135,6 +135,11 @@ SIGNATURES = {
     "onssen_tasnet_train_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _sz, _vp, _sz, _vp]),
     "onssen_tasnet_backward_workspace_bytes": (_sz, [_vp, _i, _i]),
     "onssen_tasnet_backward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "onssen_tasnet_stream_state_bytes": (_sz, [_vp, _i]),
+    "onssen_tasnet_stream_reset": (_i, [_vp, _vp, _sz, _i, _vp, _i, _vp]),
+    "onssen_tasnet_stream_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "onssen_tasnet_stream_step_f32": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "onssen_tasnet_stream_flush_f32": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp]),
 }
 
 
@@ -242,6 +247,33 @@ class Lib:
     def tasnet_backward(self, cfg, image, x, n, S, x_stride, saved, saved_bytes, d_out, d_params, ws, ws_bytes, stream):
         self.check(self.dll.onssen_tasnet_backward_f32(cfg, image, x, n, S, x_stride, saved, saved_bytes, d_out, d_params, ws,
                                                        ws_bytes, stream), "onssen_tasnet_backward_f32")
+
+    # ---- Conv-TasNet streaming inference -----------------------------------
+    def tasnet_stream_state_bytes(self, cfg, n):
+        nb = int(self.dll.onssen_tasnet_stream_state_bytes(cfg, n))
+        if nb == 0:
+            self.check(-1, "onssen_tasnet_stream_state_bytes")
+        return nb
+
+    def tasnet_stream_reset(self, cfg, state, state_bytes, n, slots, stream):
+        """``slots``: None (every stream) or a sequence of stream indices."""
+        arr = None if slots is None else (C.c_int32 * max(1, len(slots)))(*[int(v) for v in slots])
+        self.check(self.dll.onssen_tasnet_stream_reset(cfg, state, state_bytes, n, arr, 0 if slots is None else len(slots), stream),
+                   "onssen_tasnet_stream_reset")
+
+    def tasnet_stream_workspace_bytes(self, cfg, n, frames):
+        nb = int(self.dll.onssen_tasnet_stream_workspace_bytes(cfg, n, frames))
+        if nb == 0:
+            self.check(-1, "onssen_tasnet_stream_workspace_bytes")
+        return nb
+
+    def tasnet_stream_step(self, cfg, image, x_new, n, frames, x_stride, out, state, state_bytes, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_tasnet_stream_step_f32(cfg, image, x_new, n, frames, x_stride, out, state, state_bytes, ws,
+                                                          ws_bytes, stream), "onssen_tasnet_stream_step_f32")
+
+    def tasnet_stream_flush(self, cfg, image, state, state_bytes, n, out_tail, stream):
+        self.check(self.dll.onssen_tasnet_stream_flush_f32(cfg, image, state, state_bytes, n, out_tail, stream),
+                   "onssen_tasnet_stream_flush_f32")
 
     # ---- host-side wav reader (no device work) ---------------------------
     def wav_info(self, path):

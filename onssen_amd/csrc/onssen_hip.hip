@@ -112,6 +112,7 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 #include "optim.inc"
 #include "tasnet.inc"     // Conv-TasNet forward: its kernels and its C ABI entries
 #include "tasnet_bwd.inc" // Conv-TasNet training: the saving forward and the backward
+#include "tasnet_stream.inc" // Conv-TasNet streaming inference: stateful steps of causal models
 
 // Bounded waits of the persistent kernels: ~0.2 s of polling on the GPU by default.  A run-time setting of the library
 // (onssen_xcd_spin_limit), initialised from ONSSEN_XCD_SPIN_LIMIT: the host-side emulation -- where a 'workgroup' is a

@@ -158,6 +158,109 @@ class _TasNetTrainFunction(torch.autograd.Function):
         return (None, None, *grads)
 
 
+class TasNetStream:
+    """``n`` concurrent streams of a causal ConvTasNet that advance in lockstep (``ConvTasNet.stream(n)``; csrc/tasnet_stream.inc).
+
+    ``push(x)``: x (n, F hop), or (F hop,) for n = 1, hop = L/2, any F >= 1 (it may change from call to call) -> ``num_spks``
+    tensors (n, F hop).  The stream has an algorithmic delay of exactly one hop (``delay``): the first hop of output after a
+    reset is zero, and ``concat(pushes)[..., hop:]`` followed by ``flush()`` (``num_spks`` tensors (n, hop)) is bit for bit
+    ``model([x])`` of the whole signal.  ``reset(slots=None)`` starts all streams, or the given ones, over; the others are not
+    disturbed.  State (per stream: one hop of samples, every block's last (P - 1) 2^x frames, one hop of decoder taps, a frame
+    counter) and workspaces live on the device and belong to this object; a workspace is kept per F and never freed, so a
+    captured graph of a push stays valid.  ``push`` works under ``torch.cuda.graph``: the frame counters are device data,
+    so replaying the graph on a refilled static input advances the stream.  Needs eval mode and no autograd, like
+    ``forward(..., lengths=)``; the packed weights follow the parameters as for ``forward``."""
+
+    def __init__(self, model, n=1):
+        why = model.stream_limits()
+        if why:
+            raise RuntimeError("ConvTasNet: this configuration cannot stream: " + "; ".join(why))
+        if int(n) != n or not 1 <= n <= 65535:
+            raise ValueError(f"ConvTasNet.stream: n must be an integer in [1, 65535], got {n!r}")
+        self.model, self.n, self.hop = model, int(n), model.L // 2
+        self._state = None        # (device, buffer)
+        self._ws = {}             # (device, F) -> buffer
+
+    @property
+    def delay(self):
+        return self.hop
+
+    def _check_mode(self, x=None):
+        m = self.model
+        if m.training or not use_hip_path(m) or (x is not None and needs_graph(x)):
+            raise RuntimeError("ConvTasNet: streaming is an inference call: it needs eval mode and no autograd "
+                               "(torch.no_grad(), or frozen parameters)")
+
+    def _get_state(self, lib, cfg, device):
+        if self._state is None or self._state[0] != device:
+            nb = lib.tasnet_stream_state_bytes(cfg, self.n)
+            buf = torch.empty(nb, dtype=torch.uint8, device=device)
+            lib.tasnet_stream_reset(cfg, buf.data_ptr(), nb, self.n, None, _stream())
+            self._state = (device, buf)
+        return self._state[1]
+
+    def reset(self, slots=None):
+        if slots is not None:
+            slots = [int(v) for v in (slots.reshape(-1).tolist() if torch.is_tensor(slots) else slots)]
+            if any(not 0 <= v < self.n for v in slots):
+                raise ValueError(f"ConvTasNet stream: slots must lie in [0, {self.n}), got {slots!r}")
+            if not slots:
+                return
+        lib = get_lib()
+        if self._state is None:                      # nothing pushed yet: the state is created (reset) where the weights live
+            dev = self.model.encoder.weight.device
+            if dev.type == "cuda":
+                self._get_state(lib, self.model._cfg(precision()), dev)
+            return
+        buf = self._state[1]
+        lib.tasnet_stream_reset(self.model._cfg(precision()), buf.data_ptr(), buf.numel(), self.n, slots, _stream())
+
+    def push(self, x):
+        self._check_mode(x)
+        if not torch.is_tensor(x) or x.dim() not in (1, 2):
+            raise ValueError("ConvTasNet stream: push takes a 1-D or 2-D tensor of samples")
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        if x.shape[0] != self.n:
+            raise ValueError(f"ConvTasNet stream: {x.shape[0]} rows pushed into {self.n} streams")
+        if x.shape[1] == 0 or x.shape[1] % self.hop:
+            raise ValueError(f"ConvTasNet stream: a push takes a positive multiple of hop = {self.hop} samples per stream, "
+                             f"got {x.shape[1]} (the caller buffers the remainder)")
+        require_device(x, "ConvTasNet")
+        m, n, F = self.model, self.n, x.shape[1] // self.hop
+        lib = get_lib()
+        cfg = m._cfg(precision())
+        image = m._get_image(cfg)
+        x = x.float()
+        if x.stride(1) != 1 or (n > 1 and x.stride(0) < x.shape[1]):
+            x = x.contiguous()
+        x_stride = x.stride(0) if n > 1 else x.shape[1]
+        if torch.cuda.is_current_stream_capturing() and (self._state is None or self._state[0] != x.device):
+            raise RuntimeError("ConvTasNet stream: call reset() (or push once) before capturing a push: creating the state "
+                               "resets it, and a captured reset would start the stream over at every replay")
+        state = self._get_state(lib, cfg, x.device)
+        ws = self._ws.get((x.device, F))
+        if ws is None:
+            ws = self._ws[(x.device, F)] = torch.empty(lib.tasnet_stream_workspace_bytes(cfg, n, F), dtype=torch.uint8, device=x.device)
+        out = torch.empty(m.num_spks, n, F * self.hop, device=x.device, dtype=torch.float32)
+        lib.tasnet_stream_step(cfg, image.data_ptr(), x.data_ptr(), n, F, x_stride, out.data_ptr(), state.data_ptr(), state.numel(),
+                               ws.data_ptr(), ws.numel(), _stream())
+        return [out[s] for s in range(m.num_spks)]
+
+    def flush(self):
+        self._check_mode()
+        m = self.model
+        if self._state is None:
+            raise RuntimeError("ConvTasNet stream: flush before the first push")
+        lib = get_lib()
+        cfg = m._cfg(precision())
+        image = m._get_image(cfg)
+        dev, state = self._state
+        out = torch.empty(m.num_spks, self.n, self.hop, device=dev, dtype=torch.float32)
+        lib.tasnet_stream_flush(cfg, image.data_ptr(), state.data_ptr(), state.numel(), self.n, out.data_ptr(), _stream())
+        return [out[s] for s in range(m.num_spks)]
+
+
 class ConvTasNet(PackedWeightsMixin, nn.Module):
     """Drop-in for onssen.nn.ConvTasNet (onssen/nn/tasnet.py:166-264): same constructor, defaults, submodule / parameter names
     and shapes, and forward contract.
@@ -231,6 +334,23 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
         if self.X > 30:
             why.append(f"X = {self.X} > 30")
         return why
+
+    STREAM_MAX_HISTORY = 1 << 24              # ONSSEN_TASNET_STREAM_MAX_HISTORY: frames of the deepest block's history
+
+    def stream_limits(self):
+        """Reasons this model cannot run as a stream (empty: ``stream()`` works)."""
+        why = self.hip_limits()
+        if not self.causal:
+            why.append("causal = False: a non-causal block looks ahead of the frame it computes")
+        if self.norm == "gln":
+            why.append("norm = 'gln': its statistics span the whole utterance (cln and bn are local to a frame)")
+        if (self.P - 1) << max(self.X - 1, 0) > self.STREAM_MAX_HISTORY:
+            why.append(f"(P - 1) 2^(X - 1) = {(self.P - 1) << (self.X - 1)} frames of history > {self.STREAM_MAX_HISTORY}")
+        return why
+
+    def stream(self, n=1):
+        """``n`` lockstep streams of this (causal, cln / bn) model: see TasNetStream."""
+        return TasNetStream(self, n)
 
     # 1x1 convolutions kept on exact fp32 per precision (ONSSEN_TASNET_EXACT_* bits, include/onssen_hip.h).  bf16x3 keeps all four
     # kinds there: split-bf16 products (~1e-5 relative per dot product) compound over the 50 chained GEMMs of the recipe to a

@@ -55,6 +55,28 @@ def separate_tasnet(model, waves):
     return out
 
 
+@torch.no_grad()
+def separate_tasnet_stream(model, x, chunk):
+    """A whole signal through the STREAMING path of a causal ConvTasNet: x (n, S), or (S,), fed to ``model.stream(n)`` in
+    pushes of ``chunk`` hops (hop = L/2; the last push is shorter when the hops do not divide), then flushed.  Returns what
+    ``model([x])`` returns, bit for bit: the one hop of delay is trimmed and the samples beyond the last whole hop are dropped, as
+    the forward drops them.  Shows how the pieces of a stream fit together; an online caller keeps the stream object and
+    calls ``push`` as audio arrives."""
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    hop, chunk = model.L // 2, int(chunk)
+    if chunk < 1:
+        raise ValueError(f"separate_tasnet_stream: chunk must be at least one hop, got {chunk}")
+    n, S = x.shape
+    hops = S // hop
+    if hops < 2:
+        raise RuntimeError(f"ConvTasNet: {S} samples is shorter than one encoder frame (L = {model.L})")
+    st = model.stream(n)
+    pieces = [st.push(x[:, at * hop:min(at + chunk, hops) * hop]) for at in range(0, hops, chunk)]
+    tail = st.flush()
+    return [torch.squeeze(torch.cat([p[s] for p in pieces] + [tail[s]], dim=1)[:, hop:]) for s in range(model.num_spks)]
+
+
 _CLUSTER_WS = {}           # (device, B, T, F, D[, "compact"], stream) -> buffer of a uniform shape
 _CLUSTER_SCRATCH = {}      # (device, stream) -> grow-only buffer of the ragged / shape-changing calls (see dc_masks)
 _CLUSTER_PINNED = set()    # keys of _CLUSTER_WS handed out for / during a hipGraph capture: never evicted

@@ -19,7 +19,15 @@ utterances as they come; G > 1: G K read ahead and sorted by length, as tester.e
 clock starts; the legs are interleaved pass by pass in one process, warmed up, --reps device-event timed passes each.  One JSON
 line per leg: ms per utterance, median / min / max (default --out: profiles/tasnet_ragged_bench.jsonl).  The first pass also
 checks every ragged leg's estimates against the batch-1 leg's, bit for bit.
---ragged-profile K: 3 passes of the K-per-forward leg and nothing else (the run for ``rocprofv3 --kernel-trace --stats``)."""
+--ragged-profile K: 3 passes of the K-per-forward leg and nothing else (the run for ``rocprofv3 --kernel-trace --stats``).
+
+--stream: streaming inference (``ConvTasNet.stream``).  The recipe with causal=True, norm="cln"; n in {1, 16, 64} streams x
+F in {1, 8, 40} hops per step.  Legs, interleaved pass by pass in one process, --warmup passes then --reps device-event timed
+ones, median (min - max): the eager ``push``, the graph-replayed ``push``, and the only thing a causal model could do before
+there was a stream -- the (graph-replayed) offline forward over a window of receptive field + F frames per stream, of which the
+last F are kept.  One JSON line per (n, F), then one line per n with the smallest measured F whose median graph-replayed step
+stays under the chunk's own duration F hop / 8000 s (default --out: profiles/tasnet_stream_bench.jsonl).  Before timing, the
+first pushes are checked bit for bit against the offline forward."""
 import argparse
 import json
 import os
@@ -249,8 +257,76 @@ def ragged_leg(a):
             f.write(json.dumps(r) + "\n")
 
 
+def _graph(fn):
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = fn()
+    return g, out
+
+
+def stream_leg(a):
+    dev = torch.device("cuda:0")
+    c = dict(tasnet_ref.RECIPE, causal=True, norm="cln")
+    sd = tasnet_ref.make_state(c, seed=11)
+    m = onn.ConvTasNet(**c)
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    m = m.to(dev).eval()
+    hop, rate = c["L"] // 2, 8000.0
+    field = 1 + c["R"] * (c["P"] - 1) * (2 ** c["X"] - 1)          # frames one output frame depends on
+    lines, keeps_up = [], {}
+    with torch.no_grad():
+        x = torch.from_numpy((0.1 * np.random.default_rng(5).standard_normal((2, 400 * hop))).astype(np.float32)).to(dev)
+        st = m.stream(2)
+        got = torch.cat([torch.stack(st.push(x[:, i * 40 * hop:(i + 1) * 40 * hop])) for i in range(10)] + [torch.stack(st.flush())], -1)
+        assert torch.equal(got[..., hop:], torch.stack(list(m([x])))), "the stream differs from the offline forward"
+        for n in (1, 16, 64):
+            for F in (1, 8, 40):
+                chunk = torch.from_numpy((0.1 * np.random.default_rng(n + F).standard_normal((n, F * hop))).astype(np.float32)).to(dev)
+                window = torch.from_numpy((0.1 * np.random.default_rng(F).standard_normal((n, (field + F - 1) * hop + c["L"])))
+                                          .astype(np.float32)).to(dev)
+                eager, graphed = m.stream(n), m.stream(n)
+                eager.reset()
+                graphed.reset()
+                g_step, _ = _graph(lambda: graphed.push(chunk))
+                g_base, _ = _graph(lambda: m([window]))
+                legs = {"stream_eager": lambda: eager.push(chunk), "stream_graph": g_step.replay, "window_forward_graph": g_base.replay}
+                ts = {k: [] for k in legs}
+                for it in range(a.warmup + a.reps):
+                    for k, fn in legs.items():
+                        ms, _ = _timed(fn)
+                        if it >= a.warmup:
+                            ts[k].append(ms)
+                rec = {"n": n, "F": F, "chunk_ms": round(1e3 * F * hop / rate, 3), "window_frames": field + F, "reps": a.reps,
+                       "warmup": a.warmup, "precision": os.environ.get("ONSSEN_PRECISION", "bf16x3")}
+                rec.update({k: _stats(v) for k, v in ts.items()})
+                rec["window_over_stream"] = round(rec["window_forward_graph"]["median_ms"] / rec["stream_graph"]["median_ms"], 2)
+                rec["ranges_apart"] = rec["stream_graph"]["max_ms"] < rec["window_forward_graph"]["min_ms"]
+                rec["real_time"] = rec["stream_graph"]["median_ms"] < rec["chunk_ms"]
+                if rec["real_time"]:
+                    keeps_up.setdefault(n, F)
+                print(json.dumps(rec), flush=True)
+                lines.append(rec)
+                del g_step, g_base, eager, graphed
+                torch.cuda.empty_cache()
+    for n in (1, 16, 64):
+        rec = {"n": n, "smallest_measured_F_in_real_time": keeps_up.get(n)}
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+    out = a.out or os.path.join(ROOT, "profiles", "tasnet_stream_bench.jsonl")
+    with open(out, "w") as f:
+        for r in lines:
+            f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stream", action="store_true")
     ap.add_argument("--ragged", default=None, metavar="K[,K...]")
     ap.add_argument("--buckets", default="1,4")
     ap.add_argument("--ragged-profile", type=int, default=0, metavar="K")
@@ -261,6 +337,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--shapes", default=None)
     a = ap.parse_args()
+    if a.stream:
+        return stream_leg(a)
     if a.ragged or a.ragged_profile:
         return ragged_leg(a)
     if a.train or a.train_profile:
