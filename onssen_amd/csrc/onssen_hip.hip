@@ -93,6 +93,7 @@ static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 #define ONSSEN_KNOB_INT(name, dflt) (dflt)
 #endif
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool aligned256(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 255u) == 0; }
 #ifndef ONSSEN_X3Q_SMALL_DEFAULT
 #define ONSSEN_X3Q_SMALL_DEFAULT 0   // onssen_linear_x3p, bias mode: KB (32-k blocks) up to which 128 x 128 tiles run (0 = never); ONSSEN_X3Q_SMALL overrides
 #endif
@@ -113,6 +114,7 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 #include "tasnet.inc"     // Conv-TasNet forward: its kernels and its C ABI entries
 #include "tasnet_bwd.inc" // Conv-TasNet training: the saving forward and the backward
 #include "tasnet_stream.inc" // Conv-TasNet streaming inference: stateful steps of causal models
+#include "tasnet_run.inc" // Conv-TasNet: the one launch sequence behind the eval, ragged, training and stream entries
 
 // Bounded waits of the persistent kernels: ~0.2 s of polling on the GPU by default.  A run-time setting of the library
 // (onssen_xcd_spin_limit), initialised from ONSSEN_XCD_SPIN_LIMIT: the host-side emulation -- where a 'workgroup' is a

@@ -21,6 +21,11 @@
 // as a kernel argument (struct Rag; host integers in, no copy, no synchronisation), so one output element is computed by the
 // same instructions in the same order as in a one-utterance rectangular run.
 // PReLU_2 / norm_2 exist upstream but the block's forward never calls them (tasnet.py:149-163): they are not packed.
+//
+// ONE launch sequence: tas::run (tasnet_run.inc) alone walks the network.  Each entry validates its arguments and fills a Plan:
+// the kind of batch (RECT / RAGGED / STREAM picks the launch of the four boundary-aware steps) and where every activation lives;
+// the kernel variants follow from the pointers.  The two entries here work in place in the workspace (in_place()); the ragged
+// one adds its Geo tables.
 
 namespace tas {
 
@@ -104,13 +109,35 @@ static Layout layout(const Cfg& g) {
   return o;
 }
 
-// floats of the flat parameter buffer onssen_tasnet_pack_f32 reads (see include/onssen_hip.h for the order)
-static int64_t param_floats(const Cfg& g) {
-  const int64_t nb = g.norm == ONSSEN_TASNET_BN ? 4 : 2;
-  const int64_t blk = (int64_t)g.H * g.B + g.H + 1 + nb * g.H + (int64_t)g.H * g.P + g.H + (int64_t)g.B * g.H + g.B;
-  return (int64_t)g.N * g.L + 3LL * g.N + (int64_t)g.B * g.N + g.B + blk * g.R * g.X + (int64_t)g.spk * g.N * g.B +
-         (int64_t)g.spk * g.N + (int64_t)g.N * g.L + 1;
+// Offsets (floats) of the flat parameter buffer that onssen_tasnet_pack_f32 reads and onssen_tasnet_backward_f32 writes -- THE
+// order of include/onssen_hip.h: encoder, LayerN_S, bottleneck, the R X blocks, gen_masks, decoder.  norm = bn: a block also
+// carries the running mean and variance (n_mu, n_var) behind norm_1's weight and bias; they do not exist otherwise, and then
+// n_w, n_b, dw_w, dw_b are adjacent (the backward merges the four in one go).
+struct Flat {
+  int64_t enc_w, enc_b, ln_g, ln_b, bott_w, bott_b, blk0, blk_stride, mask_w, mask_b, dec_w, dec_b, total;
+  int64_t c1_w, c1_b, alpha, n_w, n_b, n_mu, n_var, dw_w, dw_b, sc_w, sc_b;     // inside a block
+};
+
+static Flat flat_layout(const Cfg& g) {
+  Flat o;
+  int64_t p = 0;
+  auto take = [&](int64_t floats) { const int64_t at = p; p += floats; return at; };
+  o.c1_w = take((int64_t)g.H * g.B); o.c1_b = take(g.H); o.alpha = take(1); o.n_w = take(g.H); o.n_b = take(g.H);
+  o.n_mu = o.n_var = p;
+  if (g.norm == ONSSEN_TASNET_BN) { o.n_mu = take(g.H); o.n_var = take(g.H); }
+  o.dw_w = take((int64_t)g.H * g.P); o.dw_b = take(g.H); o.sc_w = take((int64_t)g.B * g.H); o.sc_b = take(g.B);
+  o.blk_stride = p;
+  p = 0;
+  o.enc_w = take((int64_t)g.N * g.L); o.enc_b = take(g.N); o.ln_g = take(g.N); o.ln_b = take(g.N);
+  o.bott_w = take((int64_t)g.B * g.N); o.bott_b = take(g.B);
+  o.blk0 = take(o.blk_stride * g.R * g.X);
+  o.mask_w = take((int64_t)g.spk * g.N * g.B); o.mask_b = take((int64_t)g.spk * g.N);
+  o.dec_w = take((int64_t)g.N * g.L); o.dec_b = take(1);
+  o.total = p;
+  return o;
 }
+
+static int64_t param_floats(const Cfg& g) { return flat_layout(g).total; }
 
 // Workspace (bytes, each region 256-aligned): w [M][N], e / depthwise output [M][max(N, H)], x [M][B], c [M][H],
 // t [M][max(B, spk N)], the GEMM A-operand image [M][KBmax][2][32], statistics (max of gLN partials and cLN rows).
@@ -136,9 +163,20 @@ static Ws ws_layout_rows(const Cfg& g, size_t M, size_t nchunks) {
   return o;
 }
 
+// n utterances of S samples: T frames each, S_out samples out, M = n T rows; ok = M within the GEMMs' row bound
+struct Frames { int T, S_out; long M; bool ok; };
+static Frames frames(const Cfg& g, int n, int S) {
+  const int hop = g.L / 2, T = (S - g.L) / hop + 1;
+  const long M = (long)n * T;
+  return Frames{T, (T - 1) * hop + g.L, M, M <= 0x7fffffffL / 4};
+}
+
+// zero frames in front of a block's depthwise convolution of dilation dil
+static inline int pad_left(const Cfg& g, int dil) { return g.causal ? dil * (g.P - 1) : dil * (g.P - 1) / 2; }
+
 static Ws ws_layout(const Cfg& g, int n, int S) {
-  const int T = (S - g.L) / (g.L / 2) + 1;
-  return ws_layout_rows(g, (size_t)n * T, (size_t)n * ceil_div(T, ROWS_PER_CHUNK));
+  const Frames f = frames(g, n, S);
+  return ws_layout_rows(g, (size_t)f.M, (size_t)n * ceil_div(f.T, ROWS_PER_CHUNK));
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -299,6 +337,23 @@ __global__ __launch_bounds__(256) void tas_prelu_stats_ragged_kernel(float* __re
 }
 
 // ---- K2: norm_1 on load + dilated depthwise convolution ----------------------------------------------------------------------
+// gLN statistics of one utterance of T frames from its nch partial pairs, merged in chunk order (one thread; the forward's
+// depthwise kernel and the two backward kernels that recompute the normalised signal all call this).
+__device__ __forceinline__ void gln_stats(const double* __restrict__ part, int nch, int T, int H, float* mean, float* rstd) {
+  double s = 0.0, q = 0.0;
+  for (int i = 0; i < nch; ++i) { s += part[(long)i * 2]; q += part[(long)i * 2 + 1]; }
+  const double cnt = (double)T * H, m = s / cnt;
+  double var = q / cnt - m * m;
+  var = var > 0.0 ? var : 0.0;
+  *mean = (float)m;
+  *rstd = (float)(1.0 / sqrt(var + (double)EPS));
+}
+
+// norm_1 of one tap: (mean, rstd) of the utterance (gLN) or of the tap's frame (cLN); BatchNorm is the folded affine alone
+__device__ __forceinline__ float norm_tap(float v, float mean, float rstd, float ga, float gb, int norm) {
+  return norm == ONSSEN_TASNET_BN ? v * ga + gb : (v - mean) * rstd * ga + gb;
+}
+
 // grid (chunks of 32 frames, utterances); threads over channels.  Output frame t reads normalised frames t + d p - pad_l,
 // zeros outside [0, T).
 // One tile: output frames [t0, t0 + DW_ROWS) of the utterance of T frames whose rows start at `base`; part = that utterance's
@@ -311,15 +366,7 @@ __device__ __forceinline__ void tas_dwconv_tile(const float* __restrict__ c, lon
   __shared__ float gstat[2];
   if (threadIdx.x == 0) {
     float mean = 0.0f, rstd = 1.0f;
-    if (norm == ONSSEN_TASNET_GLN) {
-      double s = 0.0, q = 0.0;
-      for (int i = 0; i < nch; ++i) { s += part[(long)i * 2]; q += part[(long)i * 2 + 1]; }
-      const double cnt = (double)T * H, m = s / cnt;
-      double var = q / cnt - m * m;
-      var = var > 0.0 ? var : 0.0;
-      mean = (float)m;
-      rstd = (float)(1.0 / sqrt(var + (double)EPS));
-    }
+    if (norm == ONSSEN_TASNET_GLN) gln_stats(part, nch, T, H, &mean, &rstd);
     gstat[0] = mean;
     gstat[1] = rstd;
   }
@@ -334,10 +381,9 @@ __device__ __forceinline__ void tas_dwconv_tile(const float* __restrict__ c, lon
         const int tau = t + dil * p - pad_l;
         if (tau < 0 || tau >= T) continue;
         const float v = c[(base + tau) * H + k];
-        float nv;
-        if (norm == ONSSEN_TASNET_GLN) nv = (v - gmean) * grstd * ga + gb;
-        else if (norm == ONSSEN_TASNET_CLN) nv = (v - rstat[(base + tau) * 2]) * rstat[(base + tau) * 2 + 1] * ga + gb;
-        else nv = v * ga + gb;
+        const float nv = norm == ONSSEN_TASNET_GLN   ? norm_tap(v, gmean, grstd, ga, gb, norm)
+                         : norm == ONSSEN_TASNET_CLN ? norm_tap(v, rstat[(base + tau) * 2], rstat[(base + tau) * 2 + 1], ga, gb, norm)
+                                                     : norm_tap(v, 0.0f, 1.0f, ga, gb, norm);
         acc += dw[k * P + p] * nv;
       }
       out[(base + t) * H + k] = acc;
@@ -404,6 +450,13 @@ __global__ __launch_bounds__(256) void tas_mask_kernel(float* __restrict__ m, co
 // grid (chunks of 16 hop-sized output blocks, utterances, speakers).  Output block j (samples [j hop, (j + 1) hop)) is covered
 // by frames j (first half of its L taps) and j - 1 (second half); there are T + 1 blocks.  The workgroup first contracts the 17
 // frames it needs over the N channels into LDS, then every output sample is written by exactly one thread.
+// Tap l of one frame: its row r of N masked channels contracted with column l of the decoder weight [N][L], k ascending.
+__device__ __forceinline__ float dec_tap(const float* __restrict__ r, const float* __restrict__ dw, int N, int L, int l) {
+  float acc = 0.0f;
+  for (int k = 0; k < N; ++k) acc += r[k] * dw[k * L + l];
+  return acc;
+}
+
 // One tile: output blocks [j0, j0 + DEC_FRAMES) of speaker s of the utterance of T frames whose rows start at `base`; o = that
 // (speaker, utterance)'s output row of S_out valid samples.
 __device__ __forceinline__ void tas_decoder_tile(const float* __restrict__ d, long base, int T, int j0, int s, int N, int L,
@@ -415,10 +468,7 @@ __device__ __forceinline__ void tas_decoder_tile(const float* __restrict__ d, lo
   for (int e = threadIdx.x; e < (DEC_FRAMES + 1) * L; e += blockDim.x) {
     const int jj = e / L, l = e % L, f = j0 - 1 + jj;
     float acc = 0.0f;
-    if (f >= 0 && f < T) {
-      const float* r = d + (base + f) * ldd + (long)s * N;
-      for (int k = 0; k < N; ++k) acc += r[k] * dw[k * L + l];
-    }
+    if (f >= 0 && f < T) acc = dec_tap(d + (base + f) * ldd + (long)s * N, dw, N, L, l);
     Ps[jj * L + l] = acc;
   }
   __syncthreads();
@@ -466,36 +516,33 @@ static int gemm(const Cfg& g, int kind, const float* A, long M, int K, const flo
   return onssen_linear_x3p(image, (int)M, K, w3, bias, Nout, mode, 0, 0.0f, C, 1, Nout, 0, stream);
 }
 
-// What a forward needs to know about its batch.  Rectangular: n utterances of T frames.  Ragged: the tables of the four
-// boundary-aware kernels (the same row prefix sums, each with its own workgroup prefix sums) built from the host lengths.
+// The tables of a ragged batch: what the four boundary-aware kernels (encoder, statistics, depthwise convolution, decoder) need
+// to find an utterance -- the same row prefix sums, each with its own workgroup prefix sums -- built from the host lengths.
 struct Geo {
-  bool ragged;
-  int n, T, S_out;                 // rectangular
+  int S_out;                       // the longest output: the least out_stride
   long M;                          // rows in all
-  long out_stride;                 // ragged: floats per (speaker, utterance) row of out
-  Rag st, dwc, dec;                // ragged: blk = 64-frame chunks / 32-frame tiles / 16-block decoder tiles
+  long out_stride;                 // floats per (speaker, utterance) row of out
+  Rag st, dwc, dec;                // blk = 64-frame chunks / 32-frame tiles / 16-block decoder tiles
   RagChunks cs;
 };
 
 // false: a length the ragged forward refuses (n out of range, S_b < L, S_b > x_stride, M over the GEMMs' row bound)
 static bool ragged_geo(const Cfg& g, int n, const int32_t* len, int64_t x_stride, Geo* o) {
   if (n <= 0 || n > MAX_UTT || !len) return false;
-  const int hop = g.L / 2;
-  o->ragged = true;
-  o->n = o->st.n = o->dwc.n = o->dec.n = n;
-  o->T = o->S_out = 0;
+  o->st.n = o->dwc.n = o->dec.n = n;
+  o->S_out = 0;
   o->st.row[0] = o->st.blk[0] = o->dwc.blk[0] = o->dec.blk[0] = 0;
   long M = 0;
   for (int b = 0; b < n; ++b) {
     if (len[b] < g.L || (x_stride >= 0 && len[b] > x_stride)) return false;
-    const int T = (len[b] - g.L) / hop + 1, S_out = (T - 1) * hop + g.L;
-    M += T;
+    const Frames f = frames(g, 1, len[b]);
+    M += f.T;
     if (M > 0x7fffffffL / 4) return false;
-    if (S_out > o->S_out) o->S_out = S_out;                   // the longest output: the least out_stride
+    if (f.S_out > o->S_out) o->S_out = f.S_out;
     o->st.row[b + 1] = (int)M;
-    o->st.blk[b + 1] = o->st.blk[b] + ceil_div(T, ROWS_PER_CHUNK);
-    o->dwc.blk[b + 1] = o->dwc.blk[b] + ceil_div(T, DW_ROWS);
-    o->dec.blk[b + 1] = o->dec.blk[b] + ceil_div(T + 1, DEC_FRAMES);
+    o->st.blk[b + 1] = o->st.blk[b] + ceil_div(f.T, ROWS_PER_CHUNK);
+    o->dwc.blk[b + 1] = o->dwc.blk[b] + ceil_div(f.T, DW_ROWS);
+    o->dec.blk[b + 1] = o->dec.blk[b] + ceil_div(f.T + 1, DEC_FRAMES);
   }
   for (int b = 0; b <= n; ++b) {
     o->dwc.row[b] = o->dec.row[b] = o->st.row[b];
@@ -505,70 +552,41 @@ static bool ragged_geo(const Cfg& g, int n, const int32_t* len, int64_t x_stride
   return true;
 }
 
-// The forward over validated arguments: the launches of the rectangular and of the ragged entry differ in four places.
-static int forward(const Cfg& g, const void* image, const float* x, int64_t x_stride, float* out, void* ws, const Ws& w,
-                   const Geo& q, void* stream) {
-  const Layout o = layout(g);
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  const char* im = static_cast<const char*>(image);
+// ---- the plan of one run of the network (tas::run, tasnet_run.inc) -----------------------------------------------------------
+// kind: RECT = n utterances of T frames (eval and training); RAGGED = the Geo tables; STREAM = n streams advance by T frames (the
+// stage launch goes in front of the encoder, which then reads the staging rows, the history launch behind each depthwise one).
+enum Kind { RECT, RAGGED, STREAM };
+
+struct Plan {
+  Kind kind;
+  int n, T, S_out;                 // S_out: RECT
+  long M, x_stride;                // rows in all; x = the waveforms (STREAM: the new samples), rows of x_stride floats
+  const float* x;
+  float* out;
+  const Geo* geo;                  // RAGGED
+  long long* cnt;                  // STREAM: frame counters, input carry, decoder carry, staging rows, block 0's history
+  float *carry_x, *carry_d, *stage;
+  char* hist;
+  // Where the activations live.  In place (in_place(): eval, ragged, stream) they are regions of the workspace and u == c,
+  // xi == xo, logits == d; the training forward points u, y, st, the block inputs, w, e, logits and d into `saved` instead.
+  float *w, *e, *c, *t, *logits, *d;       // c = PReLU(u); t = Sc_conv's output
+  uint16_t* img;                           // the GEMMs' A-operand image
+  char *xs, *u, *y, *st;                   // block j: xi = xs + j x_step, xo = xs + (j + 1) x_step; u, y, st at + j blk_step
+  size_t x_step, blk_step;                 // (y = depthwise output, st = the statistics of norm_1)
+};
+
+static Plan in_place(Kind kind, int n, int T, long M, const float* x, long x_stride, float* out, void* ws, const Ws& w) {
   char* wb = static_cast<char*>(ws);
-  auto fi = [&](size_t off) { return reinterpret_cast<const float*>(im + off); };
-  auto ui = [&](size_t off) { return reinterpret_cast<const uint16_t*>(im + off); };
-  float *bw = reinterpret_cast<float*>(wb + w.w), *be = reinterpret_cast<float*>(wb + w.e), *bx = reinterpret_cast<float*>(wb + w.x),
-        *bc = reinterpret_cast<float*>(wb + w.c), *bt = reinterpret_cast<float*>(wb + w.t);
-  uint16_t* img = reinterpret_cast<uint16_t*>(wb + w.img);
-  double* part = reinterpret_cast<double*>(wb + w.st);
-  float* rstat = reinterpret_cast<float*>(wb + w.st);
-  const int n = q.n, T = q.T;
-  const long M = q.M;
-  // K1: encoder + LayerN_S, then the bottleneck
-  if (q.ragged)
-    hipLaunchKernelGGL(tas_encoder_ragged_kernel, dim3((unsigned)ceil_div((int)M, 4)), dim3(256), 0, st, x, (long)x_stride, q.st,
-                       g.N, g.L, fi(o.enc_w), fi(o.enc_b), fi(o.ln_g), fi(o.ln_b), bw, be);
-  else
-    hipLaunchKernelGGL(tas_encoder_kernel, dim3((unsigned)ceil_div((int)M, 4)), dim3(256), 0, st, x, (long)x_stride, T, M, g.N,
-                       g.L, fi(o.enc_w), fi(o.enc_b), fi(o.ln_g), fi(o.ln_b), bw, be);
-  ONSSEN_LAUNCH_CHECK();
-  int rc = gemm(g, ONSSEN_TASNET_EXACT_BOTTLENECK, be, M, g.N, fi(o.bott_w), ui(o.bott_x3), fi(o.bott_b), g.B, bx, img, stream);
-  if (rc) return rc;
-  const int nch = ceil_div(T, ROWS_PER_CHUNK);
-  for (int j = 0; j < g.R * g.X; ++j) {
-    const size_t k = o.blk0 + (size_t)j * o.blk_stride, k3 = o.x3_blk0 + (size_t)j * o.x3_blk_stride;
-    const int dil = 1 << (j % g.X);
-    const int pad_l = g.causal ? dil * (g.P - 1) : dil * (g.P - 1) / 2;
-    rc = gemm(g, ONSSEN_TASNET_EXACT_CONV1X1, bx, M, g.B, fi(k + o.c1_w), ui(k3 + o.c1_x3), fi(k + o.c1_b), g.H, bc, img, stream);
-    if (rc) return rc;
-    if (q.ragged) {
-      hipLaunchKernelGGL(tas_prelu_stats_ragged_kernel, dim3((unsigned)q.st.blk[n]), dim3(256), 0, st, bc, q.st, g.H, fi(k + o.alpha),
-                         g.norm, part, rstat);
-      hipLaunchKernelGGL(tas_dwconv_ragged_kernel, dim3((unsigned)q.dwc.blk[n]), dim3(256), 0, st, bc, q.dwc, q.cs, g.H, g.P, dil,
-                         pad_l, g.norm, part, rstat, fi(k + o.n_a), fi(k + o.n_b), fi(k + o.dw_w), fi(k + o.dw_b), be);
-    } else {
-      hipLaunchKernelGGL(tas_prelu_stats_kernel<false>, dim3((unsigned)nch, (unsigned)n), dim3(256), 0, st, bc, T, g.H,
-                         fi(k + o.alpha), g.norm, part, rstat, (const float*)nullptr);
-      hipLaunchKernelGGL(tas_dwconv_kernel, dim3((unsigned)ceil_div(T, DW_ROWS), (unsigned)n), dim3(256), 0, st, bc, T, g.H, g.P, dil,
-                         pad_l, g.norm, part, nch, rstat, fi(k + o.n_a), fi(k + o.n_b), fi(k + o.dw_w), fi(k + o.dw_b), be);
-    }
-    ONSSEN_LAUNCH_CHECK();
-    rc = gemm(g, ONSSEN_TASNET_EXACT_SC_CONV, be, M, g.H, fi(k + o.sc_w), ui(k3 + o.sc_x3), fi(k + o.sc_b), g.B, bt, img, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tas_residual_kernel, dim3(ew_grid(M * g.B)), dim3(256), 0, st, bx, bt, M * g.B);
-    ONSSEN_LAUNCH_CHECK();
-  }
-  rc = gemm(g, ONSSEN_TASNET_EXACT_MASKS, bx, M, g.B, fi(o.mask_w), ui(o.mask_x3), fi(o.mask_b), g.spk * g.N, bt, img, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(tas_mask_kernel<false>, dim3(ew_grid(M * g.N)), dim3(256), 0, st, bt, bw, M, g.N, g.spk, g.act,
-                     (const float*)nullptr);
-  if (q.ragged)
-    hipLaunchKernelGGL(tas_decoder_ragged_kernel, dim3((unsigned)q.dec.blk[n], (unsigned)g.spk), dim3(256), 0, st, bt, q.dec, g.N,
-                       g.L, g.spk, fi(o.dec_w), fi(o.dec_b), out, q.out_stride);
-  else
-    hipLaunchKernelGGL(tas_decoder_kernel, dim3((unsigned)ceil_div(T + 1, DEC_FRAMES), (unsigned)n, (unsigned)g.spk), dim3(256), 0,
-                       st, bt, T, g.N, g.L, g.spk, fi(o.dec_w), fi(o.dec_b), out, q.S_out);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
+  auto f = [&](size_t off) { return reinterpret_cast<float*>(wb + off); };
+  Plan p{};
+  p.kind = kind; p.n = n; p.T = T; p.M = M; p.x = x; p.x_stride = x_stride; p.out = out;
+  p.w = f(w.w); p.e = f(w.e); p.c = f(w.c); p.t = p.logits = p.d = f(w.t);
+  p.img = reinterpret_cast<uint16_t*>(wb + w.img);
+  p.xs = wb + w.x; p.u = wb + w.c; p.y = wb + w.e; p.st = wb + w.st;
+  return p;
 }
+
+static int run(const Cfg& g, const void* image, const Plan& p, void* stream);
 
 }  // namespace tas
 
@@ -591,36 +609,36 @@ int onssen_tasnet_pack_f32(const int32_t* cfg_host, const float* params, void* i
   tas::Cfg g;
   if (!tas::read_cfg(cfg_host, &g) || !params || !image) return ONSSEN_E_ARG;
   const tas::Layout o = tas::layout(g);
+  const tas::Flat fl = tas::flat_layout(g);
   if (image_bytes < o.total) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(image) & 255u) != 0) return ONSSEN_E_ALIGN;
+  if (!aligned256(image)) return ONSSEN_E_ALIGN;
   ONSSEN_CLEAR_ERROR();
   char* im = static_cast<char*>(image);
   hipStream_t st = (hipStream_t)stream;
-  const float* p = params;
   auto f = [&](size_t off) { return reinterpret_cast<float*>(im + off); };
   auto u = [&](size_t off) { return reinterpret_cast<uint16_t*>(im + off); };
-  auto copy = [&](long rows, int K, int ld, size_t off) {      // next rows x K floats of the flat buffer -> image (padded)
-    hipLaunchKernelGGL(tas::tas_copy_pad_kernel, dim3(tas::ew_grid(rows * ld)), dim3(256), 0, st, p, rows, K, ld, f(off));
-    p += rows * K;
+  auto copy = [&](int64_t at, long rows, int K, int ld, size_t off) {      // rows x K floats of the flat buffer -> image (padded)
+    hipLaunchKernelGGL(tas::tas_copy_pad_kernel, dim3(tas::ew_grid(rows * ld)), dim3(256), 0, st, params + at, rows, K, ld, f(off));
   };
   const int ldN = tas::ld4(g.N), ldB = tas::ld4(g.B), ldH = tas::ld4(g.H);
-  copy(g.N, g.L, g.L, o.enc_w); copy(1, g.N, g.N, o.enc_b); copy(1, g.N, g.N, o.ln_g); copy(1, g.N, g.N, o.ln_b);
-  copy(g.B, g.N, ldN, o.bott_w); copy(1, g.B, g.B, o.bott_b);
+  copy(fl.enc_w, g.N, g.L, g.L, o.enc_w); copy(fl.enc_b, 1, g.N, g.N, o.enc_b);
+  copy(fl.ln_g, 1, g.N, g.N, o.ln_g); copy(fl.ln_b, 1, g.N, g.N, o.ln_b);
+  copy(fl.bott_w, g.B, g.N, ldN, o.bott_w); copy(fl.bott_b, 1, g.B, g.B, o.bott_b);
   for (int j = 0; j < g.R * g.X; ++j) {
     const size_t k = o.blk0 + (size_t)j * o.blk_stride;
-    copy(g.H, g.B, ldB, k + o.c1_w); copy(1, g.H, g.H, k + o.c1_b); copy(1, 1, 1, k + o.alpha);
+    const int64_t b = fl.blk0 + j * fl.blk_stride;
+    copy(b + fl.c1_w, g.H, g.B, ldB, k + o.c1_w); copy(b + fl.c1_b, 1, g.H, g.H, k + o.c1_b); copy(b + fl.alpha, 1, 1, 1, k + o.alpha);
     if (g.norm == ONSSEN_TASNET_BN) {
-      hipLaunchKernelGGL(tas::tas_fold_bn_kernel, dim3((unsigned)ceil_div(g.H, 256)), dim3(256), 0, st, p, p + g.H, p + 2 * g.H,
-                         p + 3 * g.H, g.H, f(k + o.n_a), f(k + o.n_b));
-      p += 4 * g.H;
+      hipLaunchKernelGGL(tas::tas_fold_bn_kernel, dim3((unsigned)ceil_div(g.H, 256)), dim3(256), 0, st, params + b + fl.n_w,
+                         params + b + fl.n_b, params + b + fl.n_mu, params + b + fl.n_var, g.H, f(k + o.n_a), f(k + o.n_b));
     } else {
-      copy(1, g.H, g.H, k + o.n_a); copy(1, g.H, g.H, k + o.n_b);
+      copy(b + fl.n_w, 1, g.H, g.H, k + o.n_a); copy(b + fl.n_b, 1, g.H, g.H, k + o.n_b);
     }
-    copy(g.H, g.P, g.P, k + o.dw_w); copy(1, g.H, g.H, k + o.dw_b);
-    copy(g.B, g.H, ldH, k + o.sc_w); copy(1, g.B, g.B, k + o.sc_b);
+    copy(b + fl.dw_w, g.H, g.P, g.P, k + o.dw_w); copy(b + fl.dw_b, 1, g.H, g.H, k + o.dw_b);
+    copy(b + fl.sc_w, g.B, g.H, ldH, k + o.sc_w); copy(b + fl.sc_b, 1, g.B, g.B, k + o.sc_b);
   }
-  copy((long)g.spk * g.N, g.B, ldB, o.mask_w); copy(1, g.spk * g.N, g.spk * g.N, o.mask_b);
-  copy(g.N, g.L, g.L, o.dec_w); copy(1, 1, 1, o.dec_b);
+  copy(fl.mask_w, (long)g.spk * g.N, g.B, ldB, o.mask_w); copy(fl.mask_b, 1, g.spk * g.N, g.spk * g.N, o.mask_b);
+  copy(fl.dec_w, g.N, g.L, g.L, o.dec_w); copy(fl.dec_b, 1, 1, 1, o.dec_b);
   ONSSEN_LAUNCH_CHECK();
   // x3 images of the 1x1 weights (the split-bf16 / bf16 GEMMs' B operand) from the padded fp32 copies
   int rc = onssen_x3_image_f32(f(o.bott_w), ldN, 0, 1, g.B, g.N, u(o.bott_x3), stream);
@@ -645,13 +663,12 @@ int onssen_tasnet_forward_f32(const int32_t* cfg_host, const void* image, const 
   if (!tas::read_cfg(cfg_host, &g) || !image || !x || !out || !ws || n <= 0 || S < g.L || x_stride < S) return ONSSEN_E_ARG;
   const tas::Ws w = tas::ws_layout(g, n, S);
   if (ws_bytes < w.total) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(image) & 255u) != 0 || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0) return ONSSEN_E_ALIGN;
-  const int hop = g.L / 2, T = (S - g.L) / hop + 1, S_out = (T - 1) * hop + g.L;
-  const long M = (long)n * T;
-  if (M > 0x7fffffffL / 4) return ONSSEN_E_ARG;
-  tas::Geo q{};
-  q.ragged = false; q.n = n; q.T = T; q.S_out = S_out; q.M = M;
-  return tas::forward(g, image, x, x_stride, out, ws, w, q, stream);
+  if (!aligned256(image) || !aligned256(ws)) return ONSSEN_E_ALIGN;
+  const tas::Frames f = tas::frames(g, n, S);
+  if (!f.ok) return ONSSEN_E_ARG;
+  tas::Plan p = tas::in_place(tas::RECT, n, f.T, f.M, x, (long)x_stride, out, ws, w);
+  p.S_out = f.S_out;
+  return tas::run(g, image, p, stream);
 }
 
 size_t onssen_tasnet_ragged_workspace_bytes(const int32_t* cfg_host, int n, const int32_t* lengths_host) {
@@ -670,9 +687,11 @@ int onssen_tasnet_forward_ragged_f32(const int32_t* cfg_host, const void* image,
   if (!tas::ragged_geo(g, n, lengths_host, x_stride, &q) || out_stride < q.S_out) return ONSSEN_E_ARG;
   const tas::Ws w = tas::ws_layout_rows(g, (size_t)q.M, (size_t)q.st.blk[n]);
   if (ws_bytes < w.total) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(image) & 255u) != 0 || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0) return ONSSEN_E_ALIGN;
+  if (!aligned256(image) || !aligned256(ws)) return ONSSEN_E_ALIGN;
   q.out_stride = out_stride;
-  return tas::forward(g, image, x, x_stride, out, ws, w, q, stream);
+  tas::Plan p = tas::in_place(tas::RAGGED, n, 0, q.M, x, (long)x_stride, out, ws, w);
+  p.geo = &q;
+  return tas::run(g, image, p, stream);
 }
 
 }  // extern "C"

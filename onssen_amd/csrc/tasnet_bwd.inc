@@ -1,8 +1,10 @@
 // Conv-TasNet training: the forward that keeps what the backward needs, and the backward (gradients of every packed
 // parameter; none with respect to the waveform).  Rows and layout as in tasnet.inc: row = b * T + t, channels contiguous.
 //
-// Training forward = the kernels and the arithmetic of onssen_tasnet_forward_f32 (its output is bit-identical), writing into
-// `saved` instead of working in place.  Saved once: the encoder output w [M][N], e = LayerN_S(w) [M][N], the gen_masks logits
+// Training forward = tas::run (tasnet_run.inc), the launch sequence of onssen_tasnet_forward_f32 (its output is bit-identical),
+// over a Plan whose activations point into `saved` instead of the workspace: that alone selects tas_prelu_stats_kernel<true>,
+// tas_residual_out_kernel and tas_mask_kernel<true>.  This file keeps the `saved` layout, the backward and its workspace.
+// Saved once: the encoder output w [M][N], e = LayerN_S(w) [M][N], the gen_masks logits
 // [M][spk N] and the masked encoder output d [M][spk N]; per block: its input x_j [M][B] (R X + 1 slots: slot j + 1 is the
 // block's output), the conv1x1 output before PReLU u_j [M][H], the statistics of norm_1 (gLN: fp64 partial sums per utterance
 // and 64-frame chunk; cLN: mean / rstd per row) and the depthwise output y_j [M][H].  PReLU(u) and the normalised signal are
@@ -41,9 +43,9 @@ struct Saved {
 
 static Saved saved_layout(const Cfg& g, int n, int S) {
   Saved o;
-  const int T = (S - g.L) / (g.L / 2) + 1;
-  const size_t M = (size_t)n * T;
-  const size_t nch = (size_t)ceil_div(T, ROWS_PER_CHUNK);
+  const Frames f = frames(g, n, S);
+  const size_t M = (size_t)f.M;
+  const size_t nch = (size_t)ceil_div(f.T, ROWS_PER_CHUNK);
   const size_t st_bytes = max2((size_t)n * nch * 2 * sizeof(double), M * 2 * sizeof(float));
   size_t p = 0;
   o.w = p; p += al(M * g.N * 4);
@@ -67,10 +69,10 @@ struct Bws {
 
 static Bws bws_layout(const Cfg& g, int n, int S) {
   Bws o;
-  const int T = (S - g.L) / (g.L / 2) + 1;
-  const size_t M = (size_t)n * T;
+  const Frames f = frames(g, n, S);
+  const size_t M = (size_t)f.M;
   const size_t sN = (size_t)g.spk * g.N;
-  const size_t nchb = (size_t)ceil_div(T, BW_ROWS);
+  const size_t nchb = (size_t)ceil_div(f.T, BW_ROWS);
   size_t p = 0;
   o.gx = p; p += al(M * g.B * 4);
   o.gt = p; p += al(M * g.B * 4);
@@ -296,17 +298,6 @@ __global__ __launch_bounds__(256) void tas_mask_bwd_kernel(const float* __restri
 }
 
 // ---- depthwise convolution backward ------------------------------------------------------------------------------------------
-// The forward's statistics of one utterance (gLN) in thread 0's registers -> LDS, as tas_dwconv_kernel computes them.
-__device__ __forceinline__ void gln_stats(const double* __restrict__ part, int b, int nch, int T, int H, float* mean, float* rstd) {
-  double s = 0.0, q = 0.0;
-  for (int i = 0; i < nch; ++i) { s += part[((long)b * nch + i) * 2]; q += part[((long)b * nch + i) * 2 + 1]; }
-  const double cnt = (double)T * H, m = s / cnt;
-  double var = q / cnt - m * m;
-  var = var > 0.0 ? var : 0.0;
-  *mean = (float)m;
-  *rstd = (float)(1.0 / sqrt(var + (double)EPS));
-}
-
 // grid (chunks of BW_ROWS frames, utterances); threads over channels.  dy = gradient of the depthwise output [M][H].
 //   dz[tau][k] = sum_p dw[k][p] dy[tau - dil p + pad_l][k]  (frames outside [0, T) contribute nothing)      -> dz
 //   cpart[chunk][0 .. H)          = sum_tau dz xhat        (d norm_1.weight)
@@ -325,7 +316,7 @@ __global__ __launch_bounds__(256) void tas_dw_bwd_kernel(const float* __restrict
   const int b = blockIdx.y, nchb = gridDim.x;
   if (threadIdx.x == 0) {
     float mean = 0.0f, rstd = 1.0f;
-    if (norm == ONSSEN_TASNET_GLN) gln_stats(part, b, nch, T, H, &mean, &rstd);
+    if (norm == ONSSEN_TASNET_GLN) gln_stats(part + (long)b * nch * 2, nch, T, H, &mean, &rstd);
     gstat[0] = mean;
     gstat[1] = rstd;
   }
@@ -400,7 +391,7 @@ __global__ __launch_bounds__(256) void tas_norm_prelu_bwd_kernel(float* __restri
   if (threadIdx.x == 0) {
     float mean = 0.0f, rstd = 1.0f, c1 = 0.0f, c2 = 0.0f;
     if (norm == ONSSEN_TASNET_GLN) {
-      gln_stats(part, b, nch, T, H, &mean, &rstd);
+      gln_stats(part + (long)b * nch * 2, nch, T, H, &mean, &rstd);
       double s1 = 0.0, s2 = 0.0;
       for (int i = 0; i < nchb; ++i) { s1 += gpart[((long)b * nchb + i) * 2]; s2 += gpart[((long)b * nchb + i) * 2 + 1]; }
       c1 = (float)(s1 / ((double)T * H));
@@ -560,63 +551,21 @@ int onssen_tasnet_train_forward_f32(const int32_t* cfg_host, const void* image, 
                                     float* out, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, void* stream) {
   tas::Cfg g;
   if (!tas::train_cfg(cfg_host, &g) || !image || !x || !out || !saved || !ws || n <= 0 || S < g.L || x_stride < S) return ONSSEN_E_ARG;
-  const tas::Layout o = tas::layout(g);
   const tas::Ws w = tas::ws_layout(g, n, S);
   const tas::Saved sv = tas::saved_layout(g, n, S);
   if (ws_bytes < w.total || saved_bytes < sv.total) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(image) & 255u) != 0 || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0 ||
-      (reinterpret_cast<uintptr_t>(saved) & 255u) != 0)
-    return ONSSEN_E_ALIGN;
-  const int hop = g.L / 2, T = (S - g.L) / hop + 1, S_out = (T - 1) * hop + g.L;
-  const long M = (long)n * T;
-  if (M > 0x7fffffffL / 4) return ONSSEN_E_ARG;
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  const char* im = static_cast<const char*>(image);
-  char* wb = static_cast<char*>(ws);
+  if (!aligned256(image) || !aligned256(ws) || !aligned256(saved)) return ONSSEN_E_ALIGN;
+  const tas::Frames f = tas::frames(g, n, S);
+  if (!f.ok) return ONSSEN_E_ARG;
+  // c, t and the GEMM image stay in the workspace; everything the backward reads goes to `saved`
+  tas::Plan p = tas::in_place(tas::RECT, n, f.T, f.M, x, (long)x_stride, out, ws, w);
   char* sb = static_cast<char*>(saved);
-  auto fi = [&](size_t off) { return reinterpret_cast<const float*>(im + off); };
-  auto ui = [&](size_t off) { return reinterpret_cast<const uint16_t*>(im + off); };
   auto fs = [&](size_t off) { return reinterpret_cast<float*>(sb + off); };
-  float *bc = reinterpret_cast<float*>(wb + w.c), *bt = reinterpret_cast<float*>(wb + w.t);
-  uint16_t* img = reinterpret_cast<uint16_t*>(wb + w.img);
-  hipLaunchKernelGGL(tas::tas_encoder_kernel, dim3((unsigned)ceil_div((int)M, 4)), dim3(256), 0, st, x, (long)x_stride, T, M, g.N,
-                     g.L, fi(o.enc_w), fi(o.enc_b), fi(o.ln_g), fi(o.ln_b), fs(sv.w), fs(sv.e));
-  ONSSEN_LAUNCH_CHECK();
-  int rc = tas::gemm(g, ONSSEN_TASNET_EXACT_BOTTLENECK, fs(sv.e), M, g.N, fi(o.bott_w), ui(o.bott_x3), fi(o.bott_b), g.B, fs(sv.x0), img,
-                     stream);
-  if (rc) return rc;
-  const int nch = ceil_div(T, tas::ROWS_PER_CHUNK);
-  for (int j = 0; j < g.R * g.X; ++j) {
-    const size_t k = o.blk0 + (size_t)j * o.blk_stride, k3 = o.x3_blk0 + (size_t)j * o.x3_blk_stride;
-    const size_t sj = sv.blk0 + (size_t)j * sv.blk_stride;
-    float *xi = fs(sv.x0 + (size_t)j * sv.x_slot), *xo = fs(sv.x0 + (size_t)(j + 1) * sv.x_slot);
-    float *bu = fs(sj + sv.u), *by = fs(sj + sv.y);
-    double* part = reinterpret_cast<double*>(sb + sj + sv.st);
-    float* rstat = reinterpret_cast<float*>(sb + sj + sv.st);
-    const int dil = 1 << (j % g.X);
-    const int pad_l = g.causal ? dil * (g.P - 1) : dil * (g.P - 1) / 2;
-    rc = tas::gemm(g, ONSSEN_TASNET_EXACT_CONV1X1, xi, M, g.B, fi(k + o.c1_w), ui(k3 + o.c1_x3), fi(k + o.c1_b), g.H, bu, img, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tas::tas_prelu_stats_kernel<true>, dim3((unsigned)nch, (unsigned)n), dim3(256), 0, st, bc, T, g.H,
-                       fi(k + o.alpha), g.norm, part, rstat, (const float*)bu);
-    hipLaunchKernelGGL(tas::tas_dwconv_kernel, dim3((unsigned)ceil_div(T, tas::DW_ROWS), (unsigned)n), dim3(256), 0, st, bc, T, g.H,
-                       g.P, dil, pad_l, g.norm, part, nch, rstat, fi(k + o.n_a), fi(k + o.n_b), fi(k + o.dw_w), fi(k + o.dw_b), by);
-    ONSSEN_LAUNCH_CHECK();
-    rc = tas::gemm(g, ONSSEN_TASNET_EXACT_SC_CONV, by, M, g.H, fi(k + o.sc_w), ui(k3 + o.sc_x3), fi(k + o.sc_b), g.B, bt, img, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tas::tas_residual_out_kernel, dim3(tas::ew_grid(M * g.B)), dim3(256), 0, st, xo, xi, bt, M * g.B);
-    ONSSEN_LAUNCH_CHECK();
-  }
-  rc = tas::gemm(g, ONSSEN_TASNET_EXACT_MASKS, fs(sv.x0 + (size_t)(g.R * g.X) * sv.x_slot), M, g.B, fi(o.mask_w), ui(o.mask_x3),
-                 fi(o.mask_b), g.spk * g.N, fs(sv.logits), img, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(tas::tas_mask_kernel<true>, dim3(tas::ew_grid(M * g.N)), dim3(256), 0, st, fs(sv.d), fs(sv.w), M, g.N, g.spk, g.act,
-                     (const float*)fs(sv.logits));
-  hipLaunchKernelGGL(tas::tas_decoder_kernel, dim3((unsigned)ceil_div(T + 1, tas::DEC_FRAMES), (unsigned)n, (unsigned)g.spk),
-                     dim3(256), 0, st, fs(sv.d), T, g.N, g.L, g.spk, fi(o.dec_w), fi(o.dec_b), out, S_out);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
+  p.S_out = f.S_out;
+  p.w = fs(sv.w); p.e = fs(sv.e); p.logits = fs(sv.logits); p.d = fs(sv.d);
+  p.xs = sb + sv.x0; p.x_step = sv.x_slot;
+  p.u = sb + sv.blk0 + sv.u; p.y = sb + sv.blk0 + sv.y; p.st = sb + sv.blk0 + sv.st; p.blk_step = sv.blk_stride;
+  return tas::run(g, image, p, stream);
 }
 
 int onssen_tasnet_backward_f32(const int32_t* cfg_host, const void* image, const float* x, int n, int S, int64_t x_stride,
@@ -626,15 +575,15 @@ int onssen_tasnet_backward_f32(const int32_t* cfg_host, const void* image, const
   if (!tas::train_cfg(cfg_host, &g) || !image || !x || !saved || !d_out || !d_params || !ws || n <= 0 || S < g.L || x_stride < S)
     return ONSSEN_E_ARG;
   const tas::Layout o = tas::layout(g);
+  const tas::Flat fl = tas::flat_layout(g);              // the gradient buffer has the order of onssen_tasnet_pack_f32's params
   const tas::Saved sv = tas::saved_layout(g, n, S);
   const tas::Bws w = tas::bws_layout(g, n, S);
   if (ws_bytes < w.total || saved_bytes < sv.total) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(image) & 255u) != 0 || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0 ||
-      (reinterpret_cast<uintptr_t>(saved) & 255u) != 0)
-    return ONSSEN_E_ALIGN;
-  const int hop = g.L / 2, T = (S - g.L) / hop + 1, S_out = (T - 1) * hop + g.L;
-  const long M = (long)n * T;
-  if (M > 0x7fffffffL / 4 || M * g.spk > 0x7fffffffL / 4) return ONSSEN_E_ARG;
+  if (!aligned256(image) || !aligned256(ws) || !aligned256(saved)) return ONSSEN_E_ALIGN;
+  const tas::Frames f = tas::frames(g, n, S);
+  const int T = f.T, S_out = f.S_out;
+  const long M = f.M;
+  if (!f.ok || M * g.spk > 0x7fffffffL / 4) return ONSSEN_E_ARG;
   ONSSEN_CLEAR_ERROR();
   hipStream_t st = (hipStream_t)stream;
   const char* im = static_cast<const char*>(image);
@@ -646,11 +595,6 @@ int onssen_tasnet_backward_f32(const int32_t* cfg_host, const void* image, const
   const tas::BwdCtx c{&w, wb, st};
   const int N = g.N, L = g.L, B = g.B, H = g.H, P = g.P, sN = g.spk * g.N, RX = g.R * g.X;
   const int ldN = tas::ld4(N), ldB = tas::ld4(B), ldH = tas::ld4(H);
-  // offsets (floats) into the flat gradient buffer: the order of onssen_tasnet_pack_f32's params
-  const long p_enc_w = 0, p_enc_b = p_enc_w + (long)N * L, p_ln_g = p_enc_b + N, p_ln_b = p_ln_g + N, p_bott_w = p_ln_b + N,
-             p_bott_b = p_bott_w + (long)B * N, p_blk0 = p_bott_b + B;
-  const long blk = (long)H * B + H + 1 + 2L * H + (long)H * P + H + (long)B * H + B;
-  const long p_mask_w = p_blk0 + blk * RX, p_mask_b = p_mask_w + (long)sN * B, p_dec_w = p_mask_b + sN, p_dec_b = p_dec_w + (long)N * L;
   float *gx = fw(w.gx), *gt = fw(w.gt), *gh = fw(w.gh), *gz = fw(w.gz), *gl = fw(w.gl), *gn1 = fw(w.gn1), *gn2 = fw(w.gn2),
         *gn3 = fw(w.gn3), *fr = fw(w.fr);
   double* gst = reinterpret_cast<double*>(wb + w.gst);
@@ -660,15 +604,15 @@ int onssen_tasnet_backward_f32(const int32_t* cfg_host, const void* image, const
   const long n_out = (long)g.spk * n * S_out;
   const int sch = (int)(n_out / 4096 < 1 ? 1 : n_out / 4096 > 256 ? 256 : n_out / 4096);
   hipLaunchKernelGGL(tas::tas_sum_kernel, dim3((unsigned)sch), dim3(256), 0, st, d_out, n_out, c.part());
-  tas::merge(c, sch, 1, d_params + p_dec_b);
+  tas::merge(c, sch, 1, d_params + fl.dec_b);
   hipLaunchKernelGGL(tas::tas_frames_kernel, dim3(tas::ew_grid(M * g.spk * L)), dim3(256), 0, st, d_out, (long)n * S_out, (long)S_out, T,
                      M, g.spk, L, fr);
   hipLaunchKernelGGL(tas::tas_mask_bwd_kernel, dim3(tas::ew_grid(M * N)), dim3(256), 0, st, fs(sv.logits), fs(sv.w), fr, fi(o.dec_w), M,
                      N, L, g.spk, g.act, gl, gn1);
-  tas::wgrad(c, fs(sv.d), N, N, fr, L, L, M * g.spk, d_params + p_dec_w);
+  tas::wgrad(c, fs(sv.d), N, N, fr, L, L, M * g.spk, d_params + fl.dec_w);
   const float* x_last = fs(sv.x0 + (size_t)RX * sv.x_slot);
-  tas::wgrad(c, gl, sN, sN, x_last, B, B, M, d_params + p_mask_w);
-  tas::colsum(c, gl, sN, sN, M, d_params + p_mask_b);
+  tas::wgrad(c, gl, sN, sN, x_last, B, B, M, d_params + fl.mask_w);
+  tas::colsum(c, gl, sN, sN, M, d_params + fl.mask_b);
   ONSSEN_LAUNCH_CHECK();
   int rc = tas::dgrad(c, gl, M, sN, fi(o.mask_w), B, ldB, gx, stream);
   if (rc) return rc;
@@ -680,24 +624,23 @@ int onssen_tasnet_backward_f32(const int32_t* cfg_host, const void* image, const
     const float *xi = fs(sv.x0 + (size_t)j * sv.x_slot), *bu = fs(sj + sv.u), *by = fs(sj + sv.y);
     const double* part = reinterpret_cast<const double*>(sb + sj + sv.st);
     const float* rstat = reinterpret_cast<const float*>(sb + sj + sv.st);
-    float* dp = d_params + p_blk0 + blk * j;
-    const long q_c1_w = 0, q_c1_b = q_c1_w + (long)H * B, q_alpha = q_c1_b + H, q_n_w = q_alpha + 1,
-               q_sc_w = q_n_w + 2L * H + (long)H * P + H, q_sc_b = q_sc_w + (long)B * H;
-    const int dil = 1 << (j % g.X);
-    const int pad_l = g.causal ? dil * (P - 1) : dil * (P - 1) / 2;
-    tas::wgrad(c, gx, B, B, by, H, H, M, dp + q_sc_w);
-    tas::colsum(c, gx, B, B, M, dp + q_sc_b);
+    float* dp = d_params + fl.blk0 + fl.blk_stride * j;
+    const int dil = 1 << (j % g.X), pad_l = tas::pad_left(g, dil);
+    tas::wgrad(c, gx, B, B, by, H, H, M, dp + fl.sc_w);
+    tas::colsum(c, gx, B, B, M, dp + fl.sc_b);
     ONSSEN_LAUNCH_CHECK();
     rc = tas::dgrad(c, gx, M, B, fi(k + o.sc_w), H, ldH, gh, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(tas::tas_dw_bwd_kernel, dim3((unsigned)nchb, (unsigned)n), dim3(256), 0, st, gh, bu, T, H, P, dil, pad_l, g.norm,
                        part, nch, rstat, fi(k + o.alpha), fi(k + o.n_a), fi(k + o.n_b), fi(k + o.dw_w), gz, c.part(), gst);
-    tas::merge(c, n * nchb, (long)H * (3 + P), dp + q_n_w);
+    // ONE merge for four tensors: cpart's order [n_w | n_b | dw_w | dw_b] is Flat's, which keeps them adjacent (training has no
+    // bn, so nothing lies between n_b and dw_w): fl.dw_b + H - fl.n_w == H (3 + P)
+    tas::merge(c, n * nchb, (long)H * (3 + P), dp + fl.n_w);
     hipLaunchKernelGGL(tas::tas_norm_prelu_bwd_kernel, dim3((unsigned)nchb, (unsigned)n), dim3(256), 0, st, gz, bu, T, H, g.norm, part,
                        nch, rstat, gst, fi(k + o.alpha), fi(k + o.n_a), c.part());
-    tas::merge(c, n * nchb, 1, dp + q_alpha);
-    tas::wgrad(c, gz, H, H, xi, B, B, M, dp + q_c1_w);
-    tas::colsum(c, gz, H, H, M, dp + q_c1_b);
+    tas::merge(c, n * nchb, 1, dp + fl.alpha);
+    tas::wgrad(c, gz, H, H, xi, B, B, M, dp + fl.c1_w);
+    tas::colsum(c, gz, H, H, M, dp + fl.c1_b);
     ONSSEN_LAUNCH_CHECK();
     rc = tas::dgrad(c, gz, M, H, fi(k + o.c1_w), B, ldB, gt, stream);
     if (rc) return rc;
@@ -705,18 +648,18 @@ int onssen_tasnet_backward_f32(const int32_t* cfg_host, const void* image, const
     ONSSEN_LAUNCH_CHECK();
   }
   // 3. bottleneck, LayerN_S, encoder
-  tas::wgrad(c, gx, B, B, fs(sv.e), N, N, M, d_params + p_bott_w);
-  tas::colsum(c, gx, B, B, M, d_params + p_bott_b);
+  tas::wgrad(c, gx, B, B, fs(sv.e), N, N, M, d_params + fl.bott_w);
+  tas::colsum(c, gx, B, B, M, d_params + fl.bott_b);
   ONSSEN_LAUNCH_CHECK();
   rc = tas::dgrad(c, gx, M, B, fi(o.bott_w), N, ldN, gn2, stream);
   if (rc) return rc;
   hipLaunchKernelGGL(tas::tas_ln_bwd_kernel, dim3((unsigned)ceil_div((int)M, 4)), dim3(256), 0, st, fs(sv.w), gn2, M, N, fi(o.ln_g), gn1,
                      gn3);
-  tas::colsum(c, gn3, N, N, M, d_params + p_ln_g);
-  tas::colsum(c, gn2, N, N, M, d_params + p_ln_b);
+  tas::colsum(c, gn3, N, N, M, d_params + fl.ln_g);
+  tas::colsum(c, gn2, N, N, M, d_params + fl.ln_b);
   hipLaunchKernelGGL(tas::tas_frames_kernel, dim3(tas::ew_grid(M * L)), dim3(256), 0, st, x, 0L, (long)x_stride, T, M, 1, L, fr);
-  tas::wgrad(c, gn1, N, N, fr, L, L, M, d_params + p_enc_w);
-  tas::colsum(c, gn1, N, N, M, d_params + p_enc_b);
+  tas::wgrad(c, gn1, N, N, fr, L, L, M, d_params + fl.enc_w);
+  tas::colsum(c, gn1, N, N, M, d_params + fl.enc_b);
   ONSSEN_LAUNCH_CHECK();
   return ONSSEN_OK;
 }

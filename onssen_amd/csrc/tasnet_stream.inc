@@ -2,9 +2,11 @@
 //
 // With causal = 1 and norm in {cLN, BN} every stage of the forward is local to one encoder frame, except three that reach back:
 // the encoder frame (one hop of samples), each block's dilated depthwise convolution ((P - 1) 2^x frames) and the decoder's
-// overlap-add (one frame).  A step therefore runs the forward's own row kernels over the M = n F new frames (row = b F + t) --
-// tas_encoder_kernel on a staging row of carried hop ++ new samples, the GEMM helper, tas_prelu_stats_kernel, tas_residual_kernel,
-// tas_mask_kernel, all unchanged and all indifferent to where a row sits -- and four kernels of its own:
+// overlap-add (one frame).  A step therefore is tas::run (tasnet_run.inc) over a STREAM Plan: the forward's own launch sequence
+// and row kernels over the M = n F new frames (row = b F + t) -- tas_encoder_kernel on a staging row of carried hop ++ new
+// samples, the GEMM helper, tas_prelu_stats_kernel, tas_residual_kernel, tas_mask_kernel, all indifferent to where a row sits --
+// with the state pointers (cnt, carry_x, carry_d, the first block's history) in the plan and, at the boundary steps, the four
+// kernels of this file, which also keeps the state and workspace layouts, reset and flush:
 //   tas_stream_stage_kernel    staging rows [carried hop | new samples], the new carry, and the frame counters' advance
 //   tas_stream_dwconv_kernel   the depthwise convolution whose taps before the chunk come from the block's history ring
 //   tas_stream_history_kernel  the chunk's last min(F, history) rows (and their cLN statistics) into the ring
@@ -134,10 +136,7 @@ __global__ __launch_bounds__(256) void tas_stream_dwconv_kernel(const float* __r
           v = hist[(hbase + s) * H + k];
           if (norm == ONSSEN_TASNET_CLN) { mean = hstat[(hbase + s) * 2]; rstd = hstat[(hbase + s) * 2 + 1]; }
         }
-        float nv;
-        if (norm == ONSSEN_TASNET_CLN) nv = (v - mean) * rstd * ga + gb;
-        else nv = v * ga + gb;
-        acc += dw[k * P + p] * nv;
+        acc += dw[k * P + p] * norm_tap(v, mean, rstd, ga, gb, norm == ONSSEN_TASNET_CLN ? norm : ONSSEN_TASNET_BN);   // a stream has no gLN
       }
       out[(base + t) * H + k] = acc;
     }
@@ -178,20 +177,14 @@ __global__ __launch_bounds__(256) void tas_stream_decoder_kernel(const float* __
     const int jj = e / L, l = e % L, f = j0 - 1 + jj;
     float acc = 0.0f;
     if (f >= 0 && f < F) {
-      const float* r = d + (base + f) * ldd + (long)s * N;
-      for (int k = 0; k < N; ++k) acc += r[k] * dw[k * L + l];
+      acc = dec_tap(d + (base + f) * ldd + (long)s * N, dw, N, L, l);
     } else if (f < 0 && l >= hop) {
       acc = cr[l - hop];
     }
     Ps[jj * L + l] = acc;
   }
   if (j0 == 0)
-    for (int e = threadIdx.x; e < hop; e += blockDim.x) {
-      const float* r = d + (base + F - 1) * ldd + (long)s * N;
-      float acc = 0.0f;
-      for (int k = 0; k < N; ++k) acc += r[k] * dw[k * L + hop + e];
-      tail[e] = acc;
-    }
+    for (int e = threadIdx.x; e < hop; e += blockDim.x) tail[e] = dec_tap(d + (base + F - 1) * ldd + (long)s * N, dw, N, L, hop + e);
   __syncthreads();
   if (j0 == 0)
     for (int e = threadIdx.x; e < hop; e += blockDim.x) cr[e] = tail[e];
@@ -259,7 +252,7 @@ int onssen_tasnet_stream_reset(const int32_t* cfg_host, void* state, size_t stat
   const tas::StreamState o = tas::stream_state(g, n);
   if (o.total == 0) return ONSSEN_E_ARG;
   if (state_bytes < o.total) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(state) & 255u) != 0) return ONSSEN_E_ALIGN;
+  if (!aligned256(state)) return ONSSEN_E_ALIGN;
   ONSSEN_CLEAR_ERROR();
   hipStream_t st = (hipStream_t)stream;
   char* sb = static_cast<char*>(state);
@@ -315,69 +308,13 @@ int onssen_tasnet_stream_step_f32(const int32_t* cfg_host, const void* image, co
   if (so.total == 0) return ONSSEN_E_ARG;
   const tas::StreamWs wo = tas::stream_ws(g, n, F);
   if (state_bytes < so.total || ws_bytes < wo.total) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(image) & 255u) != 0 || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0 ||
-      (reinterpret_cast<uintptr_t>(state) & 255u) != 0)
-    return ONSSEN_E_ALIGN;
-  using namespace tas;
-  const Layout o = layout(g);
-  const Ws& w = wo.w;
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  const char* im = static_cast<const char*>(image);
-  char* sb = static_cast<char*>(state);
-  char* wb = static_cast<char*>(ws) + wo.fwd;
-  auto fi = [&](size_t off) { return reinterpret_cast<const float*>(im + off); };
-  auto ui = [&](size_t off) { return reinterpret_cast<const uint16_t*>(im + off); };
-  float *bw = reinterpret_cast<float*>(wb + w.w), *be = reinterpret_cast<float*>(wb + w.e), *bx = reinterpret_cast<float*>(wb + w.x),
-        *bc = reinterpret_cast<float*>(wb + w.c), *bt = reinterpret_cast<float*>(wb + w.t);
-  uint16_t* img = reinterpret_cast<uint16_t*>(wb + w.img);
-  double* part = reinterpret_cast<double*>(wb + w.st);
-  float* rstat = reinterpret_cast<float*>(wb + w.st);
-  float* stage = reinterpret_cast<float*>(static_cast<char*>(ws) + wo.stage);
-  long long* cnt = reinterpret_cast<long long*>(sb + so.cnt);
-  const long M = (long)n * F;
-  const long srow = (long)(F + 1) * hop;
-  hipLaunchKernelGGL(tas_stream_stage_kernel, dim3(ew_grid(n * srow)), dim3(256), 0, st, x_new, (long)x_stride, n, F, hop,
-                     reinterpret_cast<float*>(sb + so.carry_x), cnt, stage);
-  hipLaunchKernelGGL(tas_encoder_kernel, dim3((unsigned)ceil_div((int)M, 4)), dim3(256), 0, st, (const float*)stage, srow, F, M, g.N,
-                     g.L, fi(o.enc_w), fi(o.enc_b), fi(o.ln_g), fi(o.ln_b), bw, be);
-  ONSSEN_LAUNCH_CHECK();
-  int rc = gemm(g, ONSSEN_TASNET_EXACT_BOTTLENECK, be, M, g.N, fi(o.bott_w), ui(o.bott_x3), fi(o.bott_b), g.B, bx, img, stream);
-  if (rc) return rc;
-  const int nch = ceil_div(F, ROWS_PER_CHUNK);
-  size_t hp = so.blk0;
-  for (int j = 0; j < g.R * g.X; ++j) {
-    const size_t k = o.blk0 + (size_t)j * o.blk_stride, k3 = o.x3_blk0 + (size_t)j * o.x3_blk_stride;
-    const int dil = 1 << (j % g.X), hs = stream_history(g, j);
-    size_t stat_off;
-    const size_t hbytes = stream_block_bytes(g, n, j, &stat_off);
-    float *hist = reinterpret_cast<float*>(sb + hp), *hstat = reinterpret_cast<float*>(sb + hp + stat_off);
-    hp += hbytes;
-    rc = gemm(g, ONSSEN_TASNET_EXACT_CONV1X1, bx, M, g.B, fi(k + o.c1_w), ui(k3 + o.c1_x3), fi(k + o.c1_b), g.H, bc, img, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tas_prelu_stats_kernel<false>, dim3((unsigned)nch, (unsigned)n), dim3(256), 0, st, bc, F, g.H, fi(k + o.alpha),
-                       g.norm, part, rstat, (const float*)nullptr);
-    hipLaunchKernelGGL(tas_stream_dwconv_kernel, dim3((unsigned)ceil_div(F, DW_ROWS), (unsigned)n), dim3(256), 0, st, (const float*)bc,
-                       F, g.H, g.P, dil, g.norm, (const float*)rstat, (const float*)hist, (const float*)hstat, (const long long*)cnt,
-                       fi(k + o.n_a), fi(k + o.n_b), fi(k + o.dw_w), fi(k + o.dw_b), be);
-    if (hs > 0)
-      hipLaunchKernelGGL(tas_stream_history_kernel, dim3((unsigned)(F < hs ? F : hs), (unsigned)n), dim3(256), 0, st, (const float*)bc,
-                         F, g.H, hs, g.norm, (const float*)rstat, (const long long*)cnt, hist, hstat);
-    ONSSEN_LAUNCH_CHECK();
-    rc = gemm(g, ONSSEN_TASNET_EXACT_SC_CONV, be, M, g.H, fi(k + o.sc_w), ui(k3 + o.sc_x3), fi(k + o.sc_b), g.B, bt, img, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tas_residual_kernel, dim3(ew_grid(M * g.B)), dim3(256), 0, st, bx, bt, M * g.B);
-    ONSSEN_LAUNCH_CHECK();
-  }
-  rc = gemm(g, ONSSEN_TASNET_EXACT_MASKS, bx, M, g.B, fi(o.mask_w), ui(o.mask_x3), fi(o.mask_b), g.spk * g.N, bt, img, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(tas_mask_kernel<false>, dim3(ew_grid(M * g.N)), dim3(256), 0, st, bt, bw, M, g.N, g.spk, g.act,
-                     (const float*)nullptr);
-  hipLaunchKernelGGL(tas_stream_decoder_kernel, dim3((unsigned)ceil_div(F, DEC_FRAMES), (unsigned)n, (unsigned)g.spk), dim3(256), 0, st,
-                     (const float*)bt, F, g.N, g.L, g.spk, fi(o.dec_w), fi(o.dec_b), (const long long*)cnt,
-                     reinterpret_cast<float*>(sb + so.carry_d), out);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
+  if (!aligned256(image) || !aligned256(ws) || !aligned256(state)) return ONSSEN_E_ALIGN;
+  char *sb = static_cast<char*>(state), *wb = static_cast<char*>(ws);
+  tas::Plan p = tas::in_place(tas::STREAM, n, F, (long)n * F, x_new, (long)x_stride, out, wb + wo.fwd, wo.w);
+  p.cnt = reinterpret_cast<long long*>(sb + so.cnt);
+  p.carry_x = reinterpret_cast<float*>(sb + so.carry_x); p.carry_d = reinterpret_cast<float*>(sb + so.carry_d);
+  p.hist = sb + so.blk0; p.stage = reinterpret_cast<float*>(wb + wo.stage);
+  return tas::run(g, image, p, stream);
 }
 
 int onssen_tasnet_stream_flush_f32(const int32_t* cfg_host, const void* image, const void* state, size_t state_bytes, int n,
@@ -387,7 +324,7 @@ int onssen_tasnet_stream_flush_f32(const int32_t* cfg_host, const void* image, c
   const tas::StreamState so = tas::stream_state(g, n);
   if (so.total == 0) return ONSSEN_E_ARG;
   if (state_bytes < so.total) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(image) & 255u) != 0 || (reinterpret_cast<uintptr_t>(state) & 255u) != 0) return ONSSEN_E_ALIGN;
+  if (!aligned256(image) || !aligned256(state)) return ONSSEN_E_ALIGN;
   ONSSEN_CLEAR_ERROR();
   const tas::Layout o = tas::layout(g);
   const char* sb = static_cast<const char*>(state);

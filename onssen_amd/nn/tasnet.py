@@ -109,11 +109,8 @@ class _TasNetTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, x, *params):
-        lib = get_lib()
-        cfg = model._cfg(precision())
-        image = model._get_image(cfg)
+        lib, cfg, image, x, x_stride = model._hip_inputs(x)
         n, S = x.shape
-        x_stride = x.stride(0) if n > 1 else S
         hop = model.L // 2
         S_out = ((S - model.L) // hop) * hop + model.L
         dev = x.device
@@ -228,13 +225,7 @@ class TasNetStream:
                              f"got {x.shape[1]} (the caller buffers the remainder)")
         require_device(x, "ConvTasNet")
         m, n, F = self.model, self.n, x.shape[1] // self.hop
-        lib = get_lib()
-        cfg = m._cfg(precision())
-        image = m._get_image(cfg)
-        x = x.float()
-        if x.stride(1) != 1 or (n > 1 and x.stride(0) < x.shape[1]):
-            x = x.contiguous()
-        x_stride = x.stride(0) if n > 1 else x.shape[1]
+        lib, cfg, image, x, x_stride = m._hip_inputs(x)
         if torch.cuda.is_current_stream_capturing() and (self._state is None or self._state[0] != x.device):
             raise RuntimeError("ConvTasNet stream: call reset() (or push once) before capturing a push: creating the state "
                                "resets it, and a captured reset would start the stream over at every replay")
@@ -394,21 +385,30 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
         self._image = (key, image, flat)            # flat stays alive until the stream-ordered pack has read it
         return image
 
-    def _hip_forward(self, x):
+    def _hip_inputs(self, x):
+        """What every HIP entry takes -> (lib, cfg, packed image, x, x_stride): x (n, S) as fp32 with unit inner stride and rows at
+        least S apart; a size-1 batch dimension may carry any stride, so its x_stride is S."""
+        lib = get_lib()
+        cfg = self._cfg(precision())
+        image = self._get_image(cfg)
+        n, S = x.shape
+        x = x.float()
+        if x.stride(1) != 1 or (n > 1 and x.stride(0) < S):
+            x = x.contiguous()
+        return lib, cfg, image, x, (x.stride(0) if n > 1 else S)
+
+    def _require_hip_forward(self):
         why = self.hip_limits()
         if why:
             raise RuntimeError("ConvTasNet: the HIP forward cannot run this configuration: " + "; ".join(why))
+
+    def _hip_forward(self, x):
+        self._require_hip_forward()
         require_device(x, "ConvTasNet")
         n, S = x.shape
         if S < self.L:
             raise RuntimeError(f"ConvTasNet: {S} samples is shorter than one encoder frame (L = {self.L})")
-        lib = get_lib()
-        cfg = self._cfg(precision())
-        image = self._get_image(cfg)
-        x = x.float()
-        if x.stride(1) != 1 or (n > 1 and x.stride(0) < S):
-            x = x.contiguous()
-        x_stride = x.stride(0) if n > 1 else S          # a size-1 batch dimension may carry any stride
+        lib, cfg, image, x, x_stride = self._hip_inputs(x)
         hop = self.L // 2
         T = (S - self.L) // hop + 1
         S_out = (T - 1) * hop + self.L
@@ -448,19 +448,11 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
         if self.training or not use_hip_path(self) or needs_graph(x):
             raise RuntimeError("ConvTasNet: lengths= (a ragged batch of whole utterances) is an inference call: it needs eval "
                                "mode and no autograd (torch.no_grad(), or frozen parameters); training uses fixed-size chunks")
-        why = self.hip_limits()
-        if why:
-            raise RuntimeError("ConvTasNet: the HIP forward cannot run this configuration: " + "; ".join(why))
+        self._require_hip_forward()
         lengths = self._ragged_lengths(x, lengths)
         require_device(x, "ConvTasNet")
         n, S = x.shape
-        lib = get_lib()
-        cfg = self._cfg(precision())
-        image = self._get_image(cfg)
-        x = x.float()
-        if x.stride(1) != 1 or (n > 1 and x.stride(0) < S):
-            x = x.contiguous()
-        x_stride = x.stride(0) if n > 1 else S
+        lib, cfg, image, x, x_stride = self._hip_inputs(x)
         hop = self.L // 2
         S_out = max((v - self.L) // hop for v in lengths) * hop + self.L
         ln = lib.tasnet_lengths(lengths)
@@ -489,9 +481,6 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
         n, S = x.shape
         if S < self.L:
             raise RuntimeError(f"ConvTasNet: {S} samples is shorter than one encoder frame (L = {self.L})")
-        x = x.float()
-        if x.stride(1) != 1 or (n > 1 and x.stride(0) < S):
-            x = x.contiguous()
         out = _TasNetTrainFunction.apply(self, x, *self._packed_params())
         return [torch.squeeze(out[s]) for s in range(self.num_spks)]
 
