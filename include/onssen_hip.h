@@ -816,6 +816,29 @@ int onssen_tasnet_stream_step_f32(const int32_t* cfg_host, const void* image, co
 int onssen_tasnet_stream_flush_f32(const int32_t* cfg_host, const void* image, const void* state, size_t state_bytes, int n,
                                    float* out_tail, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Conv-TasNet LONG-FORM separation: a recording cut into K windows of W samples that start `step` samples apart (overlap
+ * O = W - step), each separated on its own by the forward above, and the window estimates put back together on the device.
+ * windows: x = S samples -> win = K rows of W floats (contiguous), row k = x[k step, k step + W) with zeros past S;
+ *   (K - 1) step < S.  The forward takes rows at least S apart, so overlapping windows cannot be a strided view of x.
+ * stitch: est = C x K x W window estimates (contiguous; speaker-major as the forward writes them), all windows full but the last,
+ *   which holds v_last valid samples (what lies beyond is never read); out = C x S_out, S_out = (K - 1) step + v_last;
+ *   perm_out = K x C int32, perm_out[k][c] = the row of window k that carries output channel c (perm_out[0] = identity).
+ *   Geometry: 1 <= C <= 4, K >= 1, 1 <= O <= W / 2 (at most two windows cover a sample), O < v_last <= W (every consecutive
+ *   pair overlaps in exactly O samples).  Per pair (k - 1, k): sim[i][j] = sum_t est[i][k-1][step + t] est[j][k][t] over
+ *   t in [0, O), fp64, a fixed order; the permutation pi maximising sum_i sim[i][pi(i)], scanned in lexicographic order, first
+ *   maximum wins (an all-silent overlap gives the identity); perm[k][c] = pi_k(perm[k-1][c]).  out[c][t] is a copy where one
+ *   window covers t; on an overlap, j samples into it, w_old a + w_new b with w_new = (j + 0.5) / O, w_old = 1 - w_new, a / b
+ *   the older / newer window's rows perm[k-1][c] / perm[k][c].
+ *   ws = onssen_tasnet_stitch_workspace_bytes(C, K, W, step, v_last) bytes (0: a refused geometry), 16-byte aligned, no zeroing
+ *   needed.  Nothing is read back by the host: three ordinary launches on `stream`, no atomics, two runs give the same bits.
+ * ONSSEN_E_ARG: a null pointer or a violated geometry; ONSSEN_E_WORKSPACE: ws_bytes too small; ONSSEN_E_ALIGN: ws; all before
+ *   anything is launched or written. */
+int onssen_tasnet_windows_f32(const float* x, int64_t S, int K, int W, int step, float* win, void* stream);
+size_t onssen_tasnet_stitch_workspace_bytes(int C, int K, int W, int step, int v_last);
+int onssen_tasnet_stitch_f32(const float* est, int C, int K, int W, int step, int v_last, float* out, int32_t* perm_out, void* ws,
+                             size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

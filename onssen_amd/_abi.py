@@ -140,6 +140,9 @@ SIGNATURES = {
     "onssen_tasnet_stream_workspace_bytes": (_sz, [_vp, _i, _i]),
     "onssen_tasnet_stream_step_f32": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _sz, _vp, _sz, _vp]),
     "onssen_tasnet_stream_flush_f32": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp]),
+    "onssen_tasnet_windows_f32": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),
+    "onssen_tasnet_stitch_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "onssen_tasnet_stitch_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -274,6 +277,20 @@ class Lib:
     def tasnet_stream_flush(self, cfg, image, state, state_bytes, n, out_tail, stream):
         self.check(self.dll.onssen_tasnet_stream_flush_f32(cfg, image, state, state_bytes, n, out_tail, stream),
                    "onssen_tasnet_stream_flush_f32")
+
+    # ---- Conv-TasNet long-form separation -------------------------------
+    def tasnet_windows(self, x, S, K, W, step, win, stream):
+        self.check(self.dll.onssen_tasnet_windows_f32(x, S, K, W, step, win, stream), "onssen_tasnet_windows_f32")
+
+    def tasnet_stitch_workspace_bytes(self, spk, K, W, step, v_last):
+        nb = int(self.dll.onssen_tasnet_stitch_workspace_bytes(spk, K, W, step, v_last))
+        if nb == 0:
+            self.check(-1, "onssen_tasnet_stitch_workspace_bytes")
+        return nb
+
+    def tasnet_stitch(self, est, spk, K, W, step, v_last, out, perm_out, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_tasnet_stitch_f32(est, spk, K, W, step, v_last, out, perm_out, ws, ws_bytes, stream),
+                   "onssen_tasnet_stitch_f32")
 
     # ---- host-side wav reader (no device work) ---------------------------
     def wav_info(self, path):

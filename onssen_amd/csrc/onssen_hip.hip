@@ -114,6 +114,7 @@ static inline bool aligned256(const void* p) { return (reinterpret_cast<uintptr_
 #include "tasnet.inc"     // Conv-TasNet forward: its kernels and its C ABI entries
 #include "tasnet_bwd.inc" // Conv-TasNet training: the saving forward and the backward
 #include "tasnet_stream.inc" // Conv-TasNet streaming inference: stateful steps of causal models
+#include "tasnet_stitch.inc" // Conv-TasNet long-form separation: window gather, permutation alignment, cross-fade
 #include "tasnet_run.inc" // Conv-TasNet: the one launch sequence behind the eval, ragged, training and stream entries
 
 // Bounded waits of the persistent kernels: ~0.2 s of polling on the GPU by default.  A run-time setting of the library

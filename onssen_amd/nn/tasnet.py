@@ -403,6 +403,11 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
             raise RuntimeError("ConvTasNet: the HIP forward cannot run this configuration: " + "; ".join(why))
 
     def _hip_forward(self, x):
+        out = self._hip_forward_rows(x)
+        return [torch.squeeze(out[s]) for s in range(self.num_spks)]
+
+    def _hip_forward_rows(self, x):
+        """The eval forward of x (n, S) as ONE tensor (num_spks, n, S_out), as the library writes it."""
         self._require_hip_forward()
         require_device(x, "ConvTasNet")
         n, S = x.shape
@@ -416,7 +421,7 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
         ws = self._ws.get(("tasnet", str(x.device), n, S), nb, x.device)
         out = torch.empty(self.num_spks, n, S_out, device=x.device, dtype=torch.float32)
         lib.tasnet_forward(cfg, image.data_ptr(), x.data_ptr(), n, S, x_stride, out.data_ptr(), ws.data_ptr(), nb, _stream())
-        return [torch.squeeze(out[s]) for s in range(self.num_spks)]
+        return out
 
     def _ragged_lengths(self, x, lengths):
         """``lengths`` of a ragged forward of x (n, S_max) as a list of host ints, validated."""

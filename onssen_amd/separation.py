@@ -77,6 +77,95 @@ def separate_tasnet_stream(model, x, chunk):
     return [torch.squeeze(torch.cat([p[s] for p in pieces] + [tail[s]], dim=1)[:, hop:]) for s in range(model.num_spks)]
 
 
+def tasnet_long_geometry(L, S, window, step):
+    """Windows of a long-form separation -> (S_out, K, v_last): K windows of ``window`` samples start at k ``step``; all are
+    full but the last, which holds ``v_last`` samples; S_out is what the plain forward returns for S samples.  K = 1 with
+    v_last = S_out when the signal fits one window.  Raises ValueError naming the violated requirement (hop = L/2,
+    overlap = window - step):  hop | step;  hop | (window - L), so that a window's output has exactly ``window`` samples;
+    L <= overlap <= window / 2, so that at most two windows ever cover a sample."""
+    L, S, W, step = int(L), int(S), int(window), int(step)
+    hop = L // 2
+    if step < 1 or step % hop:
+        raise ValueError(f"separate_tasnet_long: step = {step} must be a positive multiple of hop = {hop}")
+    if W < L or (W - L) % hop:
+        raise ValueError(f"separate_tasnet_long: window = {W} must be L = {L} plus a multiple of hop = {hop}, so that a "
+                         "window's output has as many samples as the window")
+    O = W - step
+    if not L <= O <= W // 2:
+        raise ValueError(f"separate_tasnet_long: overlap = window - step = {O} must lie in [L, window / 2] = [{L}, {W // 2}], "
+                         "so that consecutive windows share a frame and at most two windows cover a sample")
+    if S < L:
+        raise RuntimeError(f"ConvTasNet: {S} samples is shorter than one encoder frame (L = {L})")
+    S_out = (S - L) // hop * hop + L
+    if S_out <= W:
+        return S_out, 1, S_out
+    K = 1 + -(-(S_out - W) // step)
+    # K - 1 = ceil((S_out - W) / step):  (K - 1) step >= S_out - W gives v_last <= W, and (K - 2) step < S_out - W gives
+    # v_last = S_out - (K - 1) step > W - step = overlap.  hop divides S_out - L, step and window - L, so the last window is
+    # L plus whole hops too and its forward returns exactly v_last samples.
+    return S_out, K, S_out - (K - 1) * step
+
+
+@torch.no_grad()
+def separate_tasnet_long(model, wav, window, step=None, batch=16, return_windows=False):
+    """Long-form time-domain separation: ``wav`` (S,) on a ROCm device, of any length, is cut into windows of ``window`` samples
+    that start ``step`` apart (default: ``window // 2`` rounded down to a multiple of hop = L/2), every window is separated on
+    its own -- the gLN statistics see what they saw in training, the activations are those of ``batch`` windows -- and the
+    estimates are put back together on the device (csrc/tasnet_stitch.inc): a model assigns speakers to output rows per window,
+    so consecutive windows are permutation-aligned on their overlap (maximal summed inner product, ties to the identity) and
+    then cross-faded linearly.  Returns (num_spks, S_out), S_out what ``model([wav])`` returns; a signal that fits one window
+    IS ``model([wav])``, bit for bit.  ``return_windows=True``: also the window estimates (num_spks, K, window) -- the last
+    window holds ``S_out - (K - 1) step`` samples and zeros after them -- and ``perm`` (K, num_spks) int32, the row of window k
+    that carries output channel c.  The full windows go through the eval forward ``batch`` rows at a time, a shorter last window
+    through a forward of its own; nothing is read back by the host, so a call can be captured in a hipGraph.  Every ``norm``,
+    causal or not, up to 4 speakers; eval mode and no autograd, like ``forward(..., lengths=)``.  ``tasnet_long_geometry``
+    states the requirements on ``window`` and ``step``."""
+    from .hip import get_lib
+    from .nn._core import _stream, needs_graph, require_device, use_hip_path
+    if model.training or not use_hip_path(model) or needs_graph(wav):
+        raise RuntimeError("ConvTasNet: separate_tasnet_long is an inference call: it needs eval mode and no autograd "
+                           "(torch.no_grad(), or frozen parameters)")
+    if not torch.is_tensor(wav) or wav.dim() != 1:
+        raise ValueError("separate_tasnet_long: wav must be a 1-D tensor (samples,)")
+    model._require_hip_forward()
+    C = model.num_spks
+    if C > 4:
+        raise ValueError(f"separate_tasnet_long: num_spks = {C} > 4 (the permutation search is exhaustive)")
+    hop, W, batch = model.L // 2, int(window), int(batch)
+    if batch < 1:
+        raise ValueError(f"separate_tasnet_long: batch must be at least 1, got {batch}")
+    step = W // 2 // hop * hop if step is None else int(step)
+    S_out, K, v_last = tasnet_long_geometry(model.L, wav.shape[0], W, step)
+    require_device(wav, "ConvTasNet")
+    dev = wav.device
+    if K == 1:
+        est = model._hip_forward_rows(wav.unsqueeze(0))                    # (C, 1, S_out)
+        if return_windows:
+            return est[:, 0], est, torch.arange(C, dtype=torch.int32, device=dev).unsqueeze(0)
+        return est[:, 0]
+    lib, st = get_lib(), _stream()
+    wav = wav.float().contiguous()
+    win = torch.empty(K, W, device=dev, dtype=torch.float32)
+    lib.tasnet_windows(wav.data_ptr(), S_out, K, W, step, win.data_ptr(), st)
+    est = torch.empty(C, K, W, device=dev, dtype=torch.float32)
+    full = K if v_last == W else K - 1
+    for at in range(0, full, batch):
+        rows = model._hip_forward_rows(win[at:at + min(batch, full - at)])
+        if rows.shape[1] == K:
+            est = rows                                                      # one forward covered every window
+        else:
+            est[:, at:at + rows.shape[1]].copy_(rows)                       # (the forward writes speaker-major per call)
+    if full < K:
+        est[:, K - 1, :v_last].copy_(model._hip_forward_rows(win[K - 1:, :v_last])[:, 0])
+        est[:, K - 1, v_last:].zero_()
+    out = torch.empty(C, S_out, device=dev, dtype=torch.float32)
+    perm = torch.empty(K, C, device=dev, dtype=torch.int32)
+    nb = lib.tasnet_stitch_workspace_bytes(C, K, W, step, v_last)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    lib.tasnet_stitch(est.data_ptr(), C, K, W, step, v_last, out.data_ptr(), perm.data_ptr(), ws.data_ptr(), nb, st)
+    return (out, est, perm) if return_windows else out
+
+
 _CLUSTER_WS = {}           # (device, B, T, F, D[, "compact"], stream) -> buffer of a uniform shape
 _CLUSTER_SCRATCH = {}      # (device, stream) -> grow-only buffer of the ragged / shape-changing calls (see dc_masks)
 _CLUSTER_PINNED = set()    # keys of _CLUSTER_WS handed out for / during a hipGraph capture: never evicted

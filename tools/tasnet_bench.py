@@ -27,7 +27,16 @@ ones, median (min - max): the eager ``push``, the graph-replayed ``push``, and t
 there was a stream -- the (graph-replayed) offline forward over a window of receptive field + F frames per stream, of which the
 last F are kept.  One JSON line per (n, F), then one line per n with the smallest measured F whose median graph-replayed step
 stays under the chunk's own duration F hop / 8000 s (default --out: profiles/tasnet_stream_bench.jsonl).  Before timing, the
-first pushes are checked bit for bit against the offline forward."""
+first pushes are checked bit for bit against the offline forward.
+
+--long: long-form separation (``separation.separate_tasnet_long``).  The recipe model (gLN, non-causal); 60 s and 600 s of 8 kHz
+audio, window = 32 000, step = 16 000, --long-batch windows per forward.  Legs, interleaved pass by pass in one process, --warmup
+passes then --reps device-event timed ones, median (min - max): (a) ``separate_tasnet_long``; (b) the only thing there was before,
+one whole-signal ``forward([x])`` (if it runs out of memory, the line says so instead); and, on buffers of the same call, the gather
+launch alone and the stitch call alone (similarity + permutation + stitch launches), whose sum over (a) is the stitching share.
+One JSON line per duration with ms per second of audio (default --out: profiles/tasnet_long_bench.jsonl).
+--long-profile SECONDS: 3 calls of ``separate_tasnet_long`` on SECONDS of audio and nothing else (the run for
+``rocprofv3 --kernel-trace --stats``, which splits the share by kernel)."""
 import argparse
 import json
 import os
@@ -324,8 +333,82 @@ def stream_leg(a):
             f.write(json.dumps(r) + "\n")
 
 
+def long_leg(a):
+    from onssen_amd.hip import get_lib
+    from onssen_amd.separation import separate_tasnet_long, tasnet_long_geometry
+    dev = torch.device("cuda:0")
+    c = tasnet_ref.RECIPE
+    sd = tasnet_ref.make_state(c, seed=11)
+    m = onn.ConvTasNet(**c)
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    m = m.to(dev).eval()
+    rate, W, step, spk = 8000, 32000, 16000, c["num_spks"]
+    lib = get_lib()
+
+    def signal(seconds):
+        return torch.from_numpy((0.1 * np.random.default_rng(seconds).standard_normal(seconds * rate)).astype(np.float32)).to(dev)
+
+    if a.long_profile:
+        x = signal(a.long_profile)
+        with torch.no_grad():
+            for _ in range(3):
+                separate_tasnet_long(m, x, W, step, batch=a.long_batch)
+        torch.cuda.synchronize()
+        return
+    lines = []
+    with torch.no_grad():
+        for seconds in (60, 600):
+            x = signal(seconds)
+            S_out, K, v_last = tasnet_long_geometry(c["L"], x.shape[0], W, step)
+            out, est, perm = separate_tasnet_long(m, x, W, step, batch=a.long_batch, return_windows=True)
+            assert out.shape == (spk, S_out) and bool(torch.isfinite(out).all())
+            assert bool((perm.sort(dim=1).values == torch.arange(spk, device=dev, dtype=torch.int32)).all())
+            win = torch.empty(K, W, device=dev)
+            nb = lib.tasnet_stitch_workspace_bytes(spk, K, W, step, v_last)
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            st = torch.cuda.current_stream().cuda_stream
+            legs = {"long": lambda: separate_tasnet_long(m, x, W, step, batch=a.long_batch),
+                    "whole_forward": lambda: m([x]),
+                    "gather": lambda: lib.tasnet_windows(x.data_ptr(), S_out, K, W, step, win.data_ptr(), st),
+                    "stitch": lambda: lib.tasnet_stitch(est.data_ptr(), spk, K, W, step, v_last, out.data_ptr(), perm.data_ptr(),
+                                                        ws.data_ptr(), nb, st)}
+            rec = {"audio_s": seconds, "window": W, "step": step, "windows": K, "batch": a.long_batch, "reps": a.reps,
+                   "warmup": a.warmup, "precision": os.environ.get("ONSSEN_PRECISION", "bf16x3")}
+            try:
+                legs["whole_forward"]()
+                torch.cuda.synchronize()
+            except torch.cuda.OutOfMemoryError as e:
+                rec["whole_forward"] = "out of memory: " + str(e).splitlines()[0]
+                del legs["whole_forward"]
+                torch.cuda.empty_cache()
+            ts = {k: [] for k in legs}
+            for it in range(a.warmup + a.reps):
+                for k, fn in legs.items():
+                    ms, _ = _timed(fn)
+                    if it >= a.warmup:
+                        ts[k].append(ms)
+            for k, v in ts.items():
+                rec[k] = _stats(v)
+                rec[k]["ms_per_audio_s"] = round(rec[k]["median_ms"] / seconds, 4)
+            rec["stitching_share"] = round((rec["gather"]["median_ms"] + rec["stitch"]["median_ms"]) / rec["long"]["median_ms"], 5)
+            if "whole_forward" in ts:
+                rec["long_over_whole"] = round(rec["long"]["median_ms"] / rec["whole_forward"]["median_ms"], 3)
+            print(json.dumps(rec), flush=True)
+            lines.append(rec)
+            del x, out, est, perm, win, ws, legs
+            m._ws.cache.clear()
+            torch.cuda.empty_cache()
+    out_path = a.out or os.path.join(ROOT, "profiles", "tasnet_long_bench.jsonl")
+    with open(out_path, "w") as f:
+        for r in lines:
+            f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--long", action="store_true")
+    ap.add_argument("--long-batch", type=int, default=16)
+    ap.add_argument("--long-profile", type=int, default=0, metavar="SECONDS")
     ap.add_argument("--stream", action="store_true")
     ap.add_argument("--ragged", default=None, metavar="K[,K...]")
     ap.add_argument("--buckets", default="1,4")
@@ -337,6 +420,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--shapes", default=None)
     a = ap.parse_args()
+    if a.long or a.long_profile:
+        return long_leg(a)
     if a.stream:
         return stream_leg(a)
     if a.ragged or a.ragged_profile:
