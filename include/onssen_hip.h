@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ONSSEN_ABI_VERSION 14   /* 14 (additions, no signature changed): onssen_tasnet_stream_* (stateful streaming inference of causal Conv-TasNet models).  14 (additions, no signature changed): onssen_tasnet_forward_ragged_f32 and onssen_tasnet_ragged_workspace_bytes (Conv-TasNet over whole utterances of different lengths).  14 (additions, no signature changed): onssen_tasnet_train_forward_f32, onssen_tasnet_backward_f32 and their two size queries (Conv-TasNet training).  14 (additions, no signature changed): onssen_tasnet_* (the Conv-TasNet separation forward).  14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
+#define ONSSEN_ABI_VERSION 14   /* 14 (additions, no signature changed): onssen_sisnr_pit_* (Conv-TasNet's SI-SNR permutation-invariant training loss and its gradient).  14 (additions, no signature changed): onssen_tasnet_stream_* (stateful streaming inference of causal Conv-TasNet models).  14 (additions, no signature changed): onssen_tasnet_forward_ragged_f32 and onssen_tasnet_ragged_workspace_bytes (Conv-TasNet over whole utterances of different lengths).  14 (additions, no signature changed): onssen_tasnet_train_forward_f32, onssen_tasnet_backward_f32 and their two size queries (Conv-TasNet training).  14 (additions, no signature changed): onssen_tasnet_* (the Conv-TasNet separation forward).  14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
 
 #define ONSSEN_OK 0
 #define ONSSEN_E_ARG (-1)         /* invalid argument / unsupported shape */
@@ -576,6 +576,39 @@ int onssen_dc_head_grad_images_f32(const float* emb, const float* inv_norm, cons
 size_t onssen_batch_sdr_workspace_bytes(int B);
 int onssen_batch_sdr_f32(const float* est, const float* org, const float* mask, int B, int C, int n, float* sdr_out,
                          int* perm_out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * SI-SNR permutation-invariant training loss of Conv-TasNet, value and gradient (csrc/loss_sisnr.inc).
+ * Replaces cal_si_snr + the permutation search + the batch mean of onssen/loss/loss_e2e.py:45-87 and what autograd derives
+ * from them.  For estimates x_i and references s_j, i, j < k <= 4, each N rows of S samples, eps = 1e-8:
+ *   x~ = x - mean(x), s~ = s - mean(s), a = <x~, s~> / (|s~|^2 + eps), t = a s~,
+ *   v(i, j) = 20 log10(eps + |t| / (|x~ - t| + eps)),
+ *   value[b] = max over the permutations p of (1/k) sum_i v(i, p(i))   (lexicographic order, the first maximum wins),
+ *   perm[b]  = index of that permutation (nullable),  total[0] = -sum_b value[b] / N (nullable).
+ * The signals are passed as k base pointers with a row stride each (host arrays of device pointers / of strides in floats,
+ * stride >= S): k views of one (k, N, S_out) buffer and k separate tensors both work without a copy; any alignment is taken
+ * (rows on 16-byte boundaries are fetched 16 bytes at a time; the result does not depend on it).
+ * lengths (nullable, device int32 [N]): row b is its first lengths[b] samples for means, norms and products; its value and
+ * gradient are bit for bit those of the one-row call on that prefix, the gradient beyond it is zero, N stays the divisor.
+ * (A device value cannot be refused by the host: it is clamped to [1, S].)
+ * Degenerate rows as ATen: an all-zero or constant estimate or reference gives v = -160 and a zero gradient (a zero norm has
+ * subgradient zero); an estimate that is an exact multiple of its reference gives a finite value and gradient.
+ * One pass over the signals forward (fp64 moments per chunk, merged in a fixed order: bit-repeatable, no atomics), one
+ * elementwise pass backward:  d_est[i][b][t] = A x_i[b,t] + B s_p(i)[b,t] + C  evaluated in fp64 and rounded once, with
+ * the three fp64 coefficients per (row, estimate) the forward left in ws.  d_est is (k, N, S) contiguous and written once.
+ * g_value [N] and / or g_total [1] (device; one may be NULL): the incoming gradients of value and of total.
+ * ws: caller-owned, 8-byte aligned, onssen_sisnr_pit_workspace_bytes(N, k) bytes, needs no zeroing; the backward reads what the
+ * forward of the same batch left in it.  Refused before anything is launched or written: k < 1, k > 4, N < 1, N > 65535,
+ * S < 1, a NULL pointer, a row stride < S (ONSSEN_E_ARG); a short ws (ONSSEN_E_WORKSPACE).
+ */
+size_t onssen_sisnr_pit_workspace_bytes(int N, int k);
+int onssen_sisnr_pit_f32(const float* const* est_host, const int64_t* est_stride_host, const float* const* ref_host,
+                         const int64_t* ref_stride_host, int k, int N, int S, const int32_t* lengths, float* value,
+                         int32_t* perm, float* total, void* ws, size_t ws_bytes, void* stream);
+int onssen_sisnr_pit_backward_f32(const float* const* est_host, const int64_t* est_stride_host, const float* const* ref_host,
+                                  const int64_t* ref_stride_host, int k, int N, int S, const int32_t* lengths,
+                                  const float* g_value, const float* g_total, float* d_est, const void* ws, size_t ws_bytes,
+                                  void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K10  mask-apply + inverse STFT overlap-add.

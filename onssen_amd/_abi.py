@@ -124,6 +124,9 @@ SIGNATURES = {
     "onssen_dc_cluster_ragged_f32": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _i, _f, _vp, _vp, _sz, _i, _vp]),
     "onssen_mask_istft_ragged_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "onssen_batch_sdr_ragged_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "onssen_sisnr_pit_workspace_bytes": (_sz, [_i, _i]),
+    "onssen_sisnr_pit_f32": (_i, [_pp, C.POINTER(_i64), _pp, C.POINTER(_i64), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "onssen_sisnr_pit_backward_f32": (_i, [_pp, C.POINTER(_i64), _pp, C.POINTER(_i64), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "onssen_tasnet_param_floats": (_i64, [_vp]),
     "onssen_tasnet_image_bytes": (_sz, [_vp]),
     "onssen_tasnet_pack_f32": (_i, [_vp, _vp, _vp, _sz, _vp]),
@@ -318,6 +321,28 @@ class Lib:
             return
         self.check(self.dll.onssen_batch_sdr_f32(est, org, mask, B, Cn, n, sdr_out, perm_out, ws, ws_bytes, stream),
                    "onssen_batch_sdr_f32")
+
+    # ---- SI-SNR permutation-invariant training loss --------------------------
+    def sisnr_pit_workspace_bytes(self, N, k):
+        nb = int(self.dll.onssen_sisnr_pit_workspace_bytes(N, k))
+        if nb == 0:
+            self.check(-1, "onssen_sisnr_pit_workspace_bytes")
+        return nb
+
+    @staticmethod
+    def sisnr_signals(ptrs, strides):
+        """(host array of base pointers, host array of row strides in floats) of k signals; keep them alive across the call."""
+        k = len(ptrs)
+        return (C.c_void_p * k)(*ptrs), (C.c_int64 * k)(*[int(v) for v in strides])
+
+    def sisnr_pit(self, est, ref, k, N, S, lengths, value, perm, total, ws, ws_bytes, stream):
+        """est / ref: what ``sisnr_signals`` returns; lengths, perm, total may be None."""
+        self.check(self.dll.onssen_sisnr_pit_f32(est[0], est[1], ref[0], ref[1], k, N, S, lengths, value, perm, total, ws, ws_bytes,
+                                                 stream), "onssen_sisnr_pit_f32")
+
+    def sisnr_pit_backward(self, est, ref, k, N, S, lengths, g_value, g_total, d_est, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_sisnr_pit_backward_f32(est[0], est[1], ref[0], ref[1], k, N, S, lengths, g_value, g_total, d_est,
+                                                          ws, ws_bytes, stream), "onssen_sisnr_pit_backward_f32")
 
     def loss_mask_workspace_bytes(self, B):
         return int(self.dll.onssen_loss_mask_workspace_bytes(B))

@@ -16,6 +16,7 @@
 //                       Lloyd iterations in one persistent launch with register-resident rows; launch-per-iteration fallback)
 //   loss_sdr.inc        loss_dc_* (value and gradient) / loss_mask_* (chimera mask term: value, winning assignment, gradient),
 //                       sdr_* (batch SI-SDR with best permutation, fp64 sums)
+//   loss_sisnr.inc      sisnr_* (Conv-TasNet's SI-SNR permutation-invariant training loss: value, assignment, gradient; fp64 moments)
 //   pack.inc            one-off weight re-layout (gate permutation, MFMA fragment order, BatchNorm fold); training glue: dropout,
 //                       row-wise L2 normalisation and train-mode BatchNorm with their backward passes
 #include <hip/hip_runtime.h>
@@ -116,6 +117,7 @@ static inline bool aligned256(const void* p) { return (reinterpret_cast<uintptr_
 #include "tasnet_stream.inc" // Conv-TasNet streaming inference: stateful steps of causal models
 #include "tasnet_stitch.inc" // Conv-TasNet long-form separation: window gather, permutation alignment, cross-fade
 #include "tasnet_run.inc" // Conv-TasNet: the one launch sequence behind the eval, ragged, training and stream entries
+#include "loss_sisnr.inc" // Conv-TasNet training: the SI-SNR permutation-invariant loss and its gradient
 
 // Bounded waits of the persistent kernels: ~0.2 s of polling on the GPU by default.  A run-time setting of the library
 // (onssen_xcd_spin_limit), initialised from ONSSEN_XCD_SPIN_LIMIT: the host-side emulation -- where a 'workgroup' is a

@@ -287,8 +287,186 @@ def sisnr(x, s, eps=1e-8):
 
 def si_snr_loss(ests, refs):
     """Negative SI-SNR training loss (loss_e2e.py:72-87): per utterance the speaker-averaged sisnr of the best assignment of
-    estimates to references, summed over the batch and divided by its size."""
+    estimates to references, summed over the batch and divided by its size.
+
+    Option ``tasnet_loss`` (default "aten": the PyTorch ops below): under "hip" the value and the estimates' gradient come from
+    the SI-SNR PIT kernels (``sisnr_pit``; csrc/loss_sisnr.inc) as one autograd node, except for what ``sisnr_pit_limits`` lists,
+    which stays on the PyTorch ops by itself.  ``last_si_snr_path`` ("hip" | "aten") says which route the last call took."""
+    global last_si_snr_path
+    if options.get("tasnet_loss") == "hip" and not sisnr_pit_limits(ests, refs):
+        last_si_snr_path = "hip"
+        return _sisnr_pit_apply(list(ests), list(refs), None)[1]
+    last_si_snr_path = "aten"
     from itertools import permutations
     k = len(refs)
     per_perm = torch.stack([sum(sisnr(ests[i], refs[p[i]]) for i in range(k)) / k for p in permutations(range(k))])
     return -per_perm.max(dim=0).values.sum() / refs[0].shape[0]
+
+
+# ---- the same loss on the SI-SNR PIT kernels (csrc/loss_sisnr.inc) ---------------------------------------------------------
+last_si_snr_path = None
+SISNR_PIT_MAX_SPEAKERS = 4            # sisnr::CMAX
+SISNR_PIT_MAX_ROWS = 65535
+
+
+def sisnr_pit_limits(ests, refs):
+    """Reasons the SI-SNR PIT kernels cannot take these estimates and references (empty: they can).  Under
+    ``tasnet_loss = "hip"`` such a call stays on the PyTorch ops by itself; ``sisnr_pit`` raises with this list."""
+    ests, refs = list(ests), list(refs)
+    ts = ests + refs
+    why = []
+    if any(not t.is_cuda for t in ts):
+        why.append("CPU tensors: the kernels read ROCm device memory")
+    bad = sorted({str(t.dtype) for t in ts if t.dtype != torch.float32})
+    if bad:
+        why.append(f"dtype {', '.join(bad)}: the kernels take fp32")
+    if torch.is_grad_enabled() and any(r.requires_grad for r in refs):
+        why.append("a reference requires a gradient: the backward gives the estimates' gradient only")
+    if len(refs) > SISNR_PIT_MAX_SPEAKERS:
+        why.append(f"k = {len(refs)} > {SISNR_PIT_MAX_SPEAKERS} speakers")
+    if torch.is_anomaly_enabled():
+        why.append("autograd anomaly mode")
+    if any(t.dim() != 2 for t in ts):
+        why.append("signals that are not (N, S) matrices")
+    elif ts and ts[0].shape[0] > SISNR_PIT_MAX_ROWS:
+        why.append(f"N = {ts[0].shape[0]} > {SISNR_PIT_MAX_ROWS} rows")
+    return why
+
+
+def _pit_lengths(lengths, N, S, device):
+    """``lengths`` of a ragged batch as an int32 device tensor: host integers (a sequence or a CPU tensor) are validated and
+    copied; a device tensor is taken as it is (its values cannot be checked without reading them back: the kernels clamp them to
+    [1, S])."""
+    if lengths is None:
+        return None
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        if lengths.dtype != torch.int32 or lengths.dim() != 1:
+            raise TypeError(f"sisnr_pit: a device lengths tensor must be 1-D int32, got {lengths.dtype} with {lengths.dim()} dimensions")
+        if lengths.numel() != N:
+            raise ValueError(f"sisnr_pit: {lengths.numel()} lengths for a batch of {N} rows")
+        return lengths.contiguous()
+    if torch.is_tensor(lengths):
+        if lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+            raise TypeError(f"sisnr_pit: lengths must be integers, got {lengths.dtype}")
+        lengths = lengths.reshape(-1).tolist()
+    lengths = list(lengths)
+    if any(isinstance(v, bool) or int(v) != v for v in lengths):
+        raise TypeError(f"sisnr_pit: lengths must be integers, got {lengths!r}")
+    if len(lengths) != N:
+        raise ValueError(f"sisnr_pit: {len(lengths)} lengths for a batch of {N} rows")
+    for b, v in enumerate(lengths):
+        if not 1 <= v <= S:
+            raise ValueError(f"sisnr_pit: lengths[{b}] = {v} lies outside [1, {S}], the samples of a row")
+    return torch.tensor([int(v) for v in lengths], dtype=torch.int32, device=device)
+
+
+def _pit_rows(t):
+    """(tensor, row stride in floats) as the kernels read it: unit inner stride, rows at least S apart (any stride for one row)."""
+    N, S = t.shape
+    if t.stride(1) != 1 or (N > 1 and t.stride(0) < S):
+        t = t.contiguous()
+    return t, (t.stride(0) if N > 1 else S)
+
+
+def _pit_stacked_base(ests):
+    """The (k, N, S) tensor whose k slices the estimates are (what ConvTasNet's training forward returns), or None.  The node is
+    then applied to that tensor itself: the gradient (k, N, S) goes to it as it is written, not through k select views whose
+    gradients autograd would scatter into zeros and add (as _mask_term_hip_autograd does for the chimera masks)."""
+    base = getattr(ests[0], "_base", None)
+    k, (N, S) = len(ests), ests[0].shape
+    if base is None or not base.requires_grad or base.dtype != torch.float32 or not base.is_contiguous():
+        return None
+    if base.numel() != k * N * S or base.dim() != 3 or tuple(base.shape) != (k, N, S):
+        return None
+    for i, e in enumerate(ests):
+        if getattr(e, "_base", None) is not base or e.storage_offset() != base.storage_offset() + i * N * S:
+            return None
+        if e.stride(1) != 1 or (N > 1 and e.stride(0) != S):
+            return None
+    return base
+
+
+class _SisnrPitHip(torch.autograd.Function):
+    """(V (N,), loss, perm (N,) int32) of the SI-SNR PIT loss on onssen_sisnr_pit_f32, with the estimates' gradient from
+    onssen_sisnr_pit_backward_f32.  Two outputs carry a gradient, as _LossDcHip's: the per-row values and the scalar loss
+    -sum(V) / N, so ``si_snr_loss`` adds no reduction of its own.  ``stacked``: the first tensor is the (k, N, S) tensor
+    whose slices are the estimates; otherwise the k estimates come one by one.  The references follow; they get no gradient."""
+
+    @staticmethod
+    def forward(ctx, k, lengths, stacked, *ts):
+        from .hip import get_lib
+        lib = get_lib()
+        if stacked:
+            base, refs = ts[0], ts[1:]
+            ests = [base[i] for i in range(k)]
+        else:
+            ests, refs = ts[:k], ts[k:]
+        ests = [_pit_rows(e.detach()) for e in ests]
+        refs = [_pit_rows(r.detach()) for r in refs]
+        N, S = ests[0][0].shape
+        dev = ests[0][0].device
+        est = lib.sisnr_signals([e.data_ptr() for e, _ in ests], [st for _, st in ests])
+        ref = lib.sisnr_signals([r.data_ptr() for r, _ in refs], [st for _, st in refs])
+        nbytes = lib.sisnr_pit_workspace_bytes(N, k)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # owned by the graph: the backward reads the coefficients in it
+        value = torch.empty(N, device=dev, dtype=torch.float32)
+        total = torch.empty((), device=dev, dtype=torch.float32)
+        perm = torch.empty(N, device=dev, dtype=torch.int32)
+        lib.sisnr_pit(est, ref, k, N, S, None if lengths is None else lengths.data_ptr(), value.data_ptr(), perm.data_ptr(),
+                      total.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(perm)
+        ctx.sig = ([e for e, _ in ests], [r for r, _ in refs], est, ref, ws, lengths)
+        ctx.geom = (k, N, S, stacked, len(ts))
+        return value, total, perm
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_value, g_total, _g_perm):
+        from .hip import get_lib
+        k, N, S, stacked, n_in = ctx.geom
+        if g_value is None and g_total is None:
+            return (None,) * (3 + n_in)
+        ests, refs, est, ref, ws, lengths = ctx.sig
+        f32 = lambda g: None if g is None else g.float().contiguous()
+        g_value, g_total = f32(g_value), f32(g_total)
+        d = torch.empty(k, N, S, device=ws.device, dtype=torch.float32)
+        get_lib().sisnr_pit_backward(est, ref, k, N, S, None if lengths is None else lengths.data_ptr(),
+                                     None if g_value is None else g_value.data_ptr(), None if g_total is None else g_total.data_ptr(),
+                                     d.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+        grads = [d] if stacked else [d[i] for i in range(k)]
+        return (None, None, None, *grads, *([None] * (n_in - len(grads))))
+
+
+def _sisnr_pit_apply(ests, refs, lengths):
+    """Checks that do not depend on the route (counts, shapes: ``sisnr``'s RuntimeError text), then the node."""
+    if not ests or len(ests) != len(refs):
+        raise ValueError(f"sisnr_pit: {len(ests)} estimates for {len(refs)} references")
+    for t in ests + refs:
+        if t.shape != ests[0].shape:
+            raise RuntimeError(f"sisnr: shapes differ, {tuple(ests[0].shape)} vs {tuple(t.shape)}")
+    why = sisnr_pit_limits(ests, refs)
+    if why:
+        raise RuntimeError("sisnr_pit: the HIP kernels cannot take these inputs: " + "; ".join(why))
+    N, S = ests[0].shape
+    if S < 1 or N < 1:
+        raise RuntimeError(f"sisnr_pit: empty signals, {tuple(ests[0].shape)}")
+    lengths = _pit_lengths(lengths, N, S, ests[0].device)
+    k = len(ests)
+    base = _pit_stacked_base(ests) if torch.is_grad_enabled() else None
+    if base is not None:
+        return _SisnrPitHip.apply(k, lengths, True, base, *refs)
+    return _SisnrPitHip.apply(k, lengths, False, *ests, *refs)
+
+
+def sisnr_pit(ests, refs, lengths=None, return_perm=False):
+    """The speaker-averaged SI-SNR in dB of the best assignment of ``ests`` to ``refs`` (k tensors (N, S) each, k <= 4, fp32 on a
+    ROCm device), per row: V (N,) fp32, differentiable with respect to the estimates -- ``-V.sum() / N`` is ``si_snr_loss``.
+    ``return_perm``: also the index (N,) int64 of each row's assignment in the order of ``itertools.permutations(range(k))`` (the
+    first maximum wins).  ``lengths`` (N,), host integers or an int32 device tensor: row b is its first lengths[b] samples;
+    its value and gradient are bit for bit those of the one-row call on ``x[b, :lengths[b]]`` and the gradient beyond is zero.
+    Runs on the SI-SNR PIT kernels (csrc/loss_sisnr.inc): one pass over the signals forward, one elementwise pass backward,
+    nothing read back by the host, bit-repeatable, capturable in a graph.  Raises, with the reasons, on anything the kernels
+    cannot take (``sisnr_pit_limits``); shapes that differ raise ``sisnr``'s RuntimeError."""
+    value, _, perm = _sisnr_pit_apply(list(ests), list(refs), lengths)
+    return (value, perm.long()) if return_perm else value

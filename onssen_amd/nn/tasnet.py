@@ -279,7 +279,9 @@ class ConvTasNet(PackedWeightsMixin, nn.Module):
     Training (train mode, or a parameter gradient needed) on ROCm tensors with fp32 parameters: the network's forward AND
     backward run on HIP kernels behind one autograd node (_TasNetTrainFunction, csrc/tasnet_bwd.inc; option ``tasnet_train``,
     default "hip"), so ``loss.backward()``, ``dist.train_step``, the fused clip + Adam and the gradient reducer work on it as on
-    any module; the training forward's output is bit-identical to the eval forward's.  The loss stays on ATen ops.
+    any module; the training forward's output is bit-identical to the eval forward's.  The loss (``loss.si_snr_loss``) runs on
+    PyTorch ops by default and, under the option ``tasnet_loss = "hip"``, on the SI-SNR PIT kernels (csrc/loss_sisnr.inc) as one
+    more autograd node applied to this forward's (num_spks, n, S_out) output: a training step then runs on HIP kernels throughout.
     ``hip_train_limits()`` lists what sends a training forward to ATen autograd instead (``_autograd_forward``): what
     ``hip_limits()`` lists, ``norm="bn"``, an input that requires a gradient, anomaly mode; double backward is not offered.
     ``last_train_path`` ("hip" | "aten") says which path the last training forward took.  A CPU tensor raises unless

@@ -92,6 +92,10 @@ TABLE = {
     "tasnet_train": ("ONSSEN_TASNET_TRAIN", "hip", _choice("hip", "aten"),
                      "ConvTasNet training: hip = forward and backward of the network on the HIP kernels behind one autograd node "
                      "(gln / cln; bn, an input that requires a gradient and anomaly mode go to ATen by themselves), aten = autograd over PyTorch ops"),
+    "tasnet_loss": ("ONSSEN_TASNET_LOSS", "aten", _choice("aten", "hip"),
+                    "loss.si_snr_loss: aten = PyTorch ops over the k! assignments (default), hip = value and gradient on the SI-SNR PIT kernels as one "
+                    "autograd node (CPU tensors, a non-fp32 dtype, references that require a gradient, k > 4 and anomaly mode stay on the PyTorch ops "
+                    "by themselves)"),
     "loss": ("ONSSEN_LOSS_HIP", "1", _alias({"hip": "1", "torch": "0"}), "loss kernels on the device or PyTorch ops"),
     "fused_adam": ("ONSSEN_FUSED_ADAM", "1", _flag, "build_optimizer returns utils.ClipAdam (clipping + Adam on onssen_clip_adam_f32) for device parameters"),
     "cpu_autograd": ("ONSSEN_CPU_AUTOGRAD", "0", _flag, "TEST SCAFFOLDING, off in the product: let a training forward on CPU tensors run on ATen's LSTM so that "

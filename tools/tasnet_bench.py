@@ -10,7 +10,12 @@ shape is checked on its first 2 utterances).  Usage: python tools/tasnet_bench.p
 warmed up, median and min-max of --reps device-event timed steps each, plus forward-only (network + loss) and backward-only
 splits.  One JSON line per shape (default --out with --train: profiles/tasnet_train_bench.jsonl).
 --train-profile N: N HIP training steps at the recipe shape and nothing else -- the run to put under
-``rocprofv3 --kernel-trace --stats`` (a run of its own: profiling perturbs the timing).
+``rocprofv3 --kernel-trace --stats`` (a run of its own: profiling perturbs the timing).  --loss-route aten|hip picks the
+route of ``loss.si_snr_loss`` (option ``tasnet_loss``) for that run.
+--train-loss: the loss route as a leg of the training step.  The network on HIP (``tasnet_train`` hip) in both legs,
+``tasnet_loss`` aten against hip, same protocol and columns as --train (interleaved step by step in one process, --warmup then
+--reps device-event timed steps, median and min-max; step, forward + loss, backward), at 3 x 32 000 and 16 x 32 000.  The aten
+leg is the default route and the yardstick.  One JSON line per shape, APPENDED to profiles/tasnet_train_bench.jsonl.
 
 --ragged K[,K...]: whole-utterance evaluation.  64 utterances with seeded lengths uniform in 2 s .. 10 s at 8 kHz, recipe model,
 one pass = the eager forwards of all 64: (a) one utterance per forward (the batch-1 loop), (b) ``forward(..., lengths=)`` with K
@@ -127,6 +132,7 @@ def train_leg(a):
 
     if a.train_profile:
         os.environ["ONSSEN_TASNET_TRAIN"] = "hip"
+        os.environ["ONSSEN_TASNET_LOSS"] = a.loss_route
         n, S = 3, 32000
         rng = np.random.default_rng(5)
         xd = torch.from_numpy((0.1 * rng.standard_normal((n, S))).astype(np.float32)).to(dev)
@@ -175,6 +181,71 @@ def train_leg(a):
         torch.cuda.empty_cache()
     out = a.out or os.path.join(ROOT, "profiles", "tasnet_train_bench.jsonl")
     with open(out, "w") as f:
+        for r in lines:
+            f.write(json.dumps(r) + "\n")
+
+
+def train_loss_leg(a):
+    """The loss route (option ``tasnet_loss``) as a leg of the HIP training step: see the module docstring."""
+    from onssen_amd import dist, loss as L
+    from onssen_amd.utils import build_optimizer
+    dev = torch.device("cuda:0")
+    c = dict(tasnet_ref.RECIPE, activate="sigmoid")
+    sd = tasnet_ref.make_state(c, seed=11)
+    routes = ("aten", "hip")
+    os.environ["ONSSEN_TASNET_TRAIN"] = "hip"
+
+    def fresh():
+        m = onn.ConvTasNet(**c)
+        m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+        m = m.to(dev).train()
+        return m, build_optimizer(m.parameters(), {"name": "adam", "lr": 1e-3})
+
+    lines = []
+    for shp in a.shapes.split(","):
+        n, S = (int(v) for v in shp.split("x"))
+        rng = np.random.default_rng(5)
+        src = (0.1 * rng.standard_normal((c["num_spks"], n, S))).astype(np.float32)      # a training batch: mixture = sum of sources
+        xd = torch.from_numpy(src.sum(axis=0)).to(dev)
+        refs = [torch.from_numpy(r).to(dev) for r in src]
+        pair = {r: fresh() for r in routes}
+        step, fwd, bwd, loss0 = {r: [] for r in routes}, {r: [] for r in routes}, {r: [] for r in routes}, {}
+        for it in range(a.warmup + a.reps):                   # interleaved: aten, hip, aten, hip, ...
+            for r in routes:
+                os.environ["ONSSEN_TASNET_LOSS"] = r
+                m, opt = pair[r]
+                ms, val = _timed(lambda: dist.train_step(m, opt, L.si_snr_loss, [xd], refs))
+                assert m.last_train_path == "hip" and L.last_si_snr_path == r
+                loss0.setdefault(r, val)
+                if it >= a.warmup:
+                    step[r].append(ms)
+        for it in range(a.warmup + a.reps):                   # the splits, on the weights the steps left
+            for r in routes:
+                os.environ["ONSSEN_TASNET_LOSS"] = r
+                m, opt = pair[r]
+                m.zero_grad(set_to_none=True)
+                ms_f, loss = _timed(lambda: L.si_snr_loss(m([xd]), refs))
+                ms_b, _ = _timed(loss.backward)
+                del loss
+                if it >= a.warmup:
+                    fwd[r].append(ms_f)
+                    bwd[r].append(ms_b)
+        rec = {"leg": "loss_route", "shape": [n, S], "reps": a.reps, "warmup": a.warmup, "audio_s": n * S / 8000.0}
+        for r in routes:
+            rec["loss_" + r] = {"step": _stats(step[r]), "forward_and_loss": _stats(fwd[r]), "backward": _stats(bwd[r]),
+                                "first_loss": loss0[r]}
+        at, hp = rec["loss_aten"]["step"], rec["loss_hip"]["step"]
+        rec["aten_over_hip_step"] = round(at["median_ms"] / hp["median_ms"], 3)
+        # is the difference of the medians outside the spread of both legs?
+        rec["outside_both_spreads"] = bool(hp["max_ms"] < at["min_ms"] or at["max_ms"] < hp["min_ms"])
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+        del pair
+        torch.cuda.empty_cache()
+    for k in ("ONSSEN_TASNET_TRAIN", "ONSSEN_TASNET_LOSS"):
+        os.environ.pop(k, None)
+    out = a.out or os.path.join(ROOT, "profiles", "tasnet_train_bench.jsonl")
+    with open(out, "a") as f:
         for r in lines:
             f.write(json.dumps(r) + "\n")
 
@@ -415,6 +486,8 @@ def main():
     ap.add_argument("--ragged-profile", type=int, default=0, metavar="K")
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--train-profile", type=int, default=0)
+    ap.add_argument("--train-loss", action="store_true")
+    ap.add_argument("--loss-route", default="aten", choices=("aten", "hip"))
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
@@ -426,6 +499,9 @@ def main():
         return stream_leg(a)
     if a.ragged or a.ragged_profile:
         return ragged_leg(a)
+    if a.train_loss:
+        a.shapes = a.shapes or "3x32000,16x32000"
+        return train_loss_leg(a)
     if a.train or a.train_profile:
         a.shapes = a.shapes or "3x32000,16x32000"
         return train_leg(a)
