@@ -1,22 +1,22 @@
-// K4 BLSTM recurrence: launch-per-step kernel, XCD-local persistent kernel, launchers (part of onssen_hip.hip).
+// K4 BLSTM recurrence: launch-per-step kernel, XCD-local persistent kernel (part of onssen_hip.hip; their launchers: lstm_run.inc).
 // =================================================================================================
 // K4: one LSTM time step, both directions
 // =================================================================================================
 struct StepArgs {
-  const float* G;    // [T][B][2][NP]   input projection + biases, gate-permuted columns
-  const float* whh;  // [2][NU][KQ][NT][64][4]
-  float* y;          // [T][B][2][Hp]   layer output (h_t)
-  float* c;          // [2][B][Hp]      cell state
-  const unsigned short* whh_x3;  // split-bf16 image [2][NU][KQ2][NT][2][64][8]          (X3 kernels)
-  unsigned short* hs;            // split h hand-off in A-fragment order:
-                                 //   [2 slots][2 dirs][ceil(B/16)][KQ2][hi|lo][64 lanes][8] bf16   (X3 kernels)
-  int KQ2, Hs;                   // 32-wide k-chunks, padded row length Hs = 32*KQ2
-  int B, T, Hp, NP, KQ, NU, step;
-  long long* dbg;  // profiling only: per-step timestamps of workgroup (0,0,0), or null
-  int ablate;  // profiling only (flags >> 8): 1 = no h loads, 2 = no W loads, 4 = no MFMA, 8 = no G / c loads
-  const int* frames;  // ragged batch: frames of every batch row (<= T), or null
-  float* save_g;      // training forward: [T][B][2][NP] gate activations (i, f, g, o) in G's column layout, or null
-  float* save_c;      // training forward: [T][B][2][Hp] cell states
+  const float* G = nullptr;                // [T][B][2][NP]   input projection + biases, gate-permuted columns
+  const float* whh = nullptr;              // [2][NU][KQ][NT][64][4]
+  float* y = nullptr;                      // [T][B][2][Hp]   layer output (h_t)
+  float* c = nullptr;                      // [2][B][Hp]      cell state
+  const unsigned short* whh_x3 = nullptr;  // split-bf16 image [2][NU][KQ2][NT][2][64][8]          (X3 kernels)
+  unsigned short* hs = nullptr;            // split h hand-off in A-fragment order:
+                                           //   [2 slots][2 dirs][ceil(B/16)][KQ2][hi|lo][64 lanes][8] bf16   (X3 kernels)
+  int KQ2 = 0, Hs = 0;                     // 32-wide k-chunks, padded row length Hs = 32*KQ2
+  int B = 0, T = 0, Hp = 0, NP = 0, KQ = 0, NU = 0, step = 0;
+  long long* dbg = nullptr;                // profiling only: per-step timestamps of workgroup (0,0,0), or null
+  int ablate = 0;                          // profiling only (flags >> 8): 1 = no h loads, 2 = no W loads, 4 = no MFMA, 8 = no G / c loads
+  const int* frames = nullptr;             // ragged batch: frames of every batch row (<= T), or null
+  float* save_g = nullptr;                 // training forward: [T][B][2][NP] gate activations (i, f, g, o) in G's column layout, or null
+  float* save_c = nullptr;                 // training forward: [T][B][2][Hp] cell states
 };
 
 namespace rec {
@@ -407,37 +407,37 @@ constexpr int tile_group_size(int gi) {       // size of group gi (0 = first)
   return code % 10;
 }
 struct XcdArgs {
-  const float* G;               // [T][B][2][NP]
-  const unsigned short* whh;    // split-bf16 image [2][NU][KQ2][NT][2][64][8]
-  float* y;                     // [T][B][2][Hp]
-  unsigned short* hx;           // per group: [2 slots][KQ2][2048 B]; a chunk is [hi|lo][64][8] bf16, or -- stacked -- one
-                                // [64][8] piece whose lane (r + 16 kg) holds row r (hi) for r < RG and row r - RG (lo) above
-  unsigned* sync;               // u32 words: [256 + g] arrivals, [280] abort, u64 pairs at [320 + 4g]: max(xcc+1), max(16-xcc),
-                                // [281] status (1 = some group ran the placement-independent accesses), [282] non-finite h seen,
-                                // [288 + g] launch generation.  The block is zeroed ONCE
-                                // by the workspace owner: everything in it is monotonic, so no launch depends on a
-                                // per-launch memset reaching this XCD's L2 (hipGraph replays showed that it may not)
-  int B, T, Hp, NP, KQ2, NU, row0, nbg;
-  const unsigned short* wih0;   // FUSE_IN0: fragment image of the layer's W_ih [2][NU][KC0][NT][hi|lo][64][8], else null
-  const unsigned short* ximg;   // FUSE_IN0: x3 image of the layer's input rows [T*B][KC0][2][32]
-  const float* bias0;           // FUSE_IN0: [2*NP] packed bias (G column order)
-  int KC0;                      // FUSE_IN0: ceil(in_dim / 32) <= 5 with KCM <= 4, else 0
-  int KCM;                      // FUSE_IN0: chunks multiplied on the MFMA pipe: KC0, or KC0 - 1 when in_dim = 32*KCM + 1 (129, 257:
-                                // the lone last column is a rank-1 update on the VALU in the cell update instead)
-  const float* x0;              // FUSE_IN0 tail: fp32 input, element (b, t, k) at x0 + b*xs_b + t*xs_t + k
-  long xs_b, xs_t;
-  const float* wtail;           // FUSE_IN0 tail: column in_dim-1 of the packed W_ih, [2*NP] (G column order)
-  float* save_g;                // SAVE: [T][B][2][NP] gate activations (i, f, g, o) in G's column layout, else null
-  float* save_c;                // SAVE: [T][B][2][Hp] cell states
-  int terms;                    // 3 = split-bf16 products, 1 = plain bf16 products (ONSSEN_BLSTM_BF16)
-  int RG;                       // batch rows per exchange group: 16, or 8 / 4 when the batch is small enough to give
-                                // every XCD a group anyway (the MFMA tile stays 16 wide: see STACK)
-  unsigned spin_limit;
-  long long* dbg;               // ONSSEN_XCD_PROFILE builds: where the timestamps go, or null
-  int ablate;                   // test only: 8 = rotate groups over XCDs (the placement-independent accesses run with real cross-XCD traffic)
-  unsigned short* yimg;         // x3 image [T*B][KBI][2][32] of the layer output (the next GEMM's A operand), or null
-  int KBI;                      // ceil(2*Hp / 32)
-  const int* frames;            // RAGGED: [B] frames of every batch row (<= T): a row holds h = c = 0 at t >= frames[b], or null
+  const float* G = nullptr;               // [T][B][2][NP]
+  const unsigned short* whh = nullptr;    // split-bf16 image [2][NU][KQ2][NT][2][64][8]
+  float* y = nullptr;                     // [T][B][2][Hp]
+  unsigned short* hx = nullptr;           // per group: [2 slots][KQ2][2048 B]; a chunk is [hi|lo][64][8] bf16, or -- stacked -- one
+                                          // [64][8] piece whose lane (r + 16 kg) holds row r (hi) for r < RG and row r - RG (lo) above
+  unsigned* sync = nullptr;               // u32 words: [256 + g] arrivals, [280] abort, u64 pairs at [320 + 4g]: max(xcc+1), max(16-xcc),
+                                          // [281] status (1 = some group ran the placement-independent accesses), [282] non-finite h seen,
+                                          // [288 + g] launch generation.  The block is zeroed ONCE
+                                          // by the workspace owner: everything in it is monotonic, so no launch depends on a
+                                          // per-launch memset reaching this XCD's L2 (hipGraph replays showed that it may not)
+  int B = 0, T = 0, Hp = 0, NP = 0, KQ2 = 0, NU = 0, row0 = 0, nbg = 0;
+  const unsigned short* wih0 = nullptr;   // FUSE_IN0: fragment image of the layer's W_ih [2][NU][KC0][NT][hi|lo][64][8], else null
+  const unsigned short* ximg = nullptr;   // FUSE_IN0: x3 image of the layer's input rows [T*B][KC0][2][32]
+  const float* bias0 = nullptr;           // FUSE_IN0: [2*NP] packed bias (G column order)
+  int KC0 = 0;                            // FUSE_IN0: ceil(in_dim / 32) <= 5 with KCM <= 4, else 0
+  int KCM = 0;                            // FUSE_IN0: chunks multiplied on the MFMA pipe: KC0, or KC0 - 1 when in_dim = 32*KCM + 1 (129, 257:
+                                          // the lone last column is a rank-1 update on the VALU in the cell update instead)
+  const float* x0 = nullptr;              // FUSE_IN0 tail: fp32 input, element (b, t, k) at x0 + b*xs_b + t*xs_t + k
+  long xs_b = 0, xs_t = 0;
+  const float* wtail = nullptr;           // FUSE_IN0 tail: column in_dim-1 of the packed W_ih, [2*NP] (G column order)
+  float* save_g = nullptr;                // SAVE: [T][B][2][NP] gate activations (i, f, g, o) in G's column layout, else null
+  float* save_c = nullptr;                // SAVE: [T][B][2][Hp] cell states
+  int terms = 0;                          // 3 = split-bf16 products, 1 = plain bf16 products (ONSSEN_BLSTM_BF16)
+  int RG = 0;                             // batch rows per exchange group: 16, or 8 / 4 when the batch is small enough to give
+                                          // every XCD a group anyway (the MFMA tile stays 16 wide: see STACK)
+  unsigned spin_limit = 0;
+  long long* dbg = nullptr;               // ONSSEN_XCD_PROFILE builds: where the timestamps go, or null
+  int ablate = 0;                         // test only: 8 = rotate groups over XCDs (the placement-independent accesses run with real cross-XCD traffic)
+  unsigned short* yimg = nullptr;         // x3 image [T*B][KBI][2][32] of the layer output (the next GEMM's A operand), or null
+  int KBI = 0;                            // ceil(2*Hp / 32)
+  const int* frames = nullptr;            // RAGGED: [B] frames of every batch row (<= T): a row holds h = c = 0 at t >= frames[b], or null
   // PAIR launch (round 6, onssen_blstm_pipe2_forward_f32): the batch groups bg >= nbg_a of a launch are a SECOND recurrence -- another
   // layer's weights and input projection over the same rows [row0, row0 + nbg_a RG) -- that shares nothing with the first but the launch:
   // layer 1 of batch n-1 on one half of the XCDs, layer 0 of batch n on the other (16-row groups: the B = 64 cost per time step for
@@ -1276,120 +1276,6 @@ __global__ __launch_bounds__(64 * NW) void lstm_xcd_kernel(XcdArgs p) {
     __syncthreads();
     for (int i = tid; i < STN * 24; i += NTHR) p.dbg[i] = stamp_s[i];
   }
-}
-
-// ---- launchers ----------------------------------------------------------------------------------
-template <int NT>
-static int launch_xcd(XcdArgs xa, int nw, hipStream_t st) {
-  // <= 4 batch groups per launch (2 directions x 4 = the chip's 8 XCDs)
-  // rows per group: the smallest of 4 / 8 / 16 that still covers the batch with the chip's 8 groups per launch
-  xa.RG = xa.B <= 16 ? 4 : xa.B <= 32 ? 8 : 16;
-  static const int rg_env = ONSSEN_KNOB_INT("ONSSEN_XCD_RG", 0);   // profiling: force 4 / 8 / 16
-  if (rg_env == 4 || rg_env == 8 || rg_env == 16) xa.RG = rg_env;
-  // ragged batches promise every row the bits of its own batch-1 run, which is a STACKED 4-row group: the stacked tile adds the
-  // lo x lo products that the 16-row form drops, so more than 32 rows run as several launches of 8-row groups instead
-  if (xa.frames) xa.RG = xa.B <= 16 ? 4 : 8;
-  static const int stack_env = ONSSEN_KNOB_INT("ONSSEN_XCD_STACK", 1);   // profiling: 0 = never stack
-  const bool stack = xa.RG <= 8 && xa.terms == 3 && stack_env != 0;
-  for (int r0 = 0; r0 < xa.B; r0 += 4 * xa.RG) {
-    const int rows = xa.B - r0 < 4 * xa.RG ? xa.B - r0 : 4 * xa.RG;
-    xa.row0 = r0;
-    xa.nbg = ceil_div(rows, xa.RG);
-    const bool fz = xa.KC0 > 0;
-    const dim3 grid((unsigned)(8 * xa.NU));
-#define ONSSEN_XCD_LAUNCH(NW_, FZ_, TERMS_, STACK_, SAVE_) \
-  hipLaunchKernelGGL((lstm_xcd_kernel<NT, NW_, FZ_, TERMS_, STACK_, SAVE_>), grid, dim3(64 * NW_), 0, st, xa)
-#define ONSSEN_XCD_LAUNCH_RAGGED(NW_) \
-  hipLaunchKernelGGL((lstm_xcd_kernel<NT, NW_, false, 3, true, false, true>), grid, dim3(64 * NW_), 0, st, xa)
-#define ONSSEN_XCD_FORMS(NW_)                                                                      \
-  do {                                                                                             \
-    if (xa.frames) {   /* ragged batch of whole utterances (split-bf16, unfused, inference) */       \
-      if (!stack) return ONSSEN_E_ARG;                                                             \
-      ONSSEN_XCD_LAUNCH_RAGGED(NW_);                                                               \
-    } else if (xa.save_c) {   /* training forward: keeps gates and cell states for the backward kernels */ \
-      if (stack) ONSSEN_XCD_LAUNCH(NW_, false, 3, true, true); else ONSSEN_XCD_LAUNCH(NW_, false, 3, false, true); \
-    } else if (xa.terms == 0) {   /* exact fp32 (no ONSSEN_BLSTM_BF16X3) */                        \
-      ONSSEN_XCD_LAUNCH(NW_, false, 0, false, false);                                              \
-    } else if (xa.terms == 1) {   /* plain bf16 products (ONSSEN_BLSTM_BF16) */                    \
-      if (fz) ONSSEN_XCD_LAUNCH(NW_, true, 1, false, false); else ONSSEN_XCD_LAUNCH(NW_, false, 1, false, false); \
-    } else if (stack) {                                                                            \
-      if (fz) ONSSEN_XCD_LAUNCH(NW_, true, 3, true, false); else ONSSEN_XCD_LAUNCH(NW_, false, 3, true, false); \
-    } else {                                                                                       \
-      if (fz) ONSSEN_XCD_LAUNCH(NW_, true, 3, false, false); else ONSSEN_XCD_LAUNCH(NW_, false, 3, false, false); \
-    }                                                                                              \
-  } while (0)
-    (void)nw;
-    ONSSEN_XCD_FORMS(8);
-#undef ONSSEN_XCD_FORMS
-#undef ONSSEN_XCD_LAUNCH
-#undef ONSSEN_XCD_LAUNCH_RAGGED
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ONSSEN_OK : (int)e;
-}
-
-// PAIR launch (XcdArgs::nbg_a): two plain split-bf16 recurrences over the same B <= 32 rows in ONE launch, each on its own half of
-// the XCDs -- 16-row groups above 16 rows (the unstacked three-term tile), stacked 8-row groups up to 16
-template <int NT>
-static int launch_xcd_pair(XcdArgs xa, hipStream_t st) {
-  if (xa.B > 32 || xa.terms != 3 || xa.KC0 > 0 || xa.save_c || !xa.G_b || !xa.whh_b || !xa.yimg_b) return ONSSEN_E_ARG;
-  // ragged rows promise the bits of their own batch-1 run, which is a stacked tile: <= 16 rows (8-row groups), both halves ragged
-  if ((xa.frames != nullptr) != (xa.frames_b != nullptr) || (xa.frames && xa.B > 16)) return ONSSEN_E_ARG;
-  xa.RG = xa.B <= 16 ? 8 : 16;
-  xa.row0 = 0;
-  xa.nbg_a = ceil_div(xa.B, xa.RG);
-  xa.nbg = 2 * xa.nbg_a;
-  const dim3 grid((unsigned)(8 * xa.NU));
-  if (xa.frames) hipLaunchKernelGGL((lstm_xcd_kernel<NT, 8, false, 3, true, false, true>), grid, dim3(512), 0, st, xa);
-  else if (xa.RG == 8) hipLaunchKernelGGL((lstm_xcd_kernel<NT, 8, false, 3, true, false>), grid, dim3(512), 0, st, xa);
-  else hipLaunchKernelGGL((lstm_xcd_kernel<NT, 8, false, 3, false, false>), grid, dim3(512), 0, st, xa);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ONSSEN_OK : (int)e;
-}
-
-// ug = 24 (640 < H <= 768, round 4): NT = 6 gate tiles per member, 32 members = every CU of the XCD; the plain split-bf16
-// recurrence only (stacked / unstacked / ragged, and the training forward with saved state) -- W_hh takes 144 of the 256 registers
-static int launch_xcd_wide(XcdArgs xa, hipStream_t st) {
-  if (xa.terms != 3 || xa.KC0 > 0 || (xa.save_c && xa.frames)) return ONSSEN_E_ARG;
-  xa.RG = xa.B <= 16 ? 4 : xa.B <= 32 ? 8 : 16;
-  if (xa.frames) xa.RG = xa.B <= 16 ? 4 : 8;
-  const bool stack = xa.RG <= 8;
-  for (int r0 = 0; r0 < xa.B; r0 += 4 * xa.RG) {
-    const int rows = xa.B - r0 < 4 * xa.RG ? xa.B - r0 : 4 * xa.RG;
-    xa.row0 = r0;
-    xa.nbg = ceil_div(rows, xa.RG);
-    const dim3 grid((unsigned)(8 * xa.NU));
-    if (xa.frames) hipLaunchKernelGGL((lstm_xcd_kernel<6, 8, false, 3, true, false, true>), grid, dim3(512), 0, st, xa);
-    else if (xa.save_c && stack) hipLaunchKernelGGL((lstm_xcd_kernel<6, 8, false, 3, true, true, false>), grid, dim3(512), 0, st, xa);      // training forward (243 VGPRs, no spill)
-    else if (xa.save_c) hipLaunchKernelGGL((lstm_xcd_kernel<6, 8, false, 3, false, true, false>), grid, dim3(512), 0, st, xa);
-    else if (stack) hipLaunchKernelGGL((lstm_xcd_kernel<6, 8, false, 3, true, false, false>), grid, dim3(512), 0, st, xa);
-    else hipLaunchKernelGGL((lstm_xcd_kernel<6, 8, false, 3, false, false, false>), grid, dim3(512), 0, st, xa);
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ONSSEN_OK : (int)e;
-}
-
-template <int MT, int NT>
-static int launch_steps(StepArgs sp, char* ws, int T, bool x3, hipStream_t st) {
-  const dim3 grid((unsigned)sp.NU, 2, (unsigned)ceil_div(sp.B, 16 * MT)), block(256);
-  const unsigned g_off = (unsigned)(((const char*)sp.G - ws) / 256), c_off = (unsigned)(((char*)sp.c - ws) / 256),
-                 hs_off = (unsigned)(((char*)sp.hs - ws) / 256);
-  ONSSEN_CLEAR_ERROR();
-  for (int s = 0; s < T; ++s) {
-    sp.step = s;
-    const void* w = x3 ? (const void*)sp.whh_x3 : (const void*)sp.whh;
-#define ONSSEN_STEP_LAUNCH(X3_, DBG_)                                                                             \
-  hipLaunchKernelGGL((lstm_step_kernel<MT, NT, X3_, DBG_>), grid, block, 0, st, w, ws, sp.y, s, sp.B, sp.NU, T, g_off, \
-                     c_off, hs_off, sp.ablate, sp.dbg, sp.frames, sp.save_g, sp.save_c)
-    if (sp.ablate || sp.dbg || sp.frames || sp.save_g) {
-      if (x3) ONSSEN_STEP_LAUNCH(true, true); else ONSSEN_STEP_LAUNCH(false, true);
-    } else {
-      if (x3) ONSSEN_STEP_LAUNCH(true, false); else ONSSEN_STEP_LAUNCH(false, false);
-    }
-#undef ONSSEN_STEP_LAUNCH
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ONSSEN_OK : (int)e;
 }
 
 // calibration probe: a chain of n dependent near-empty launches (measures the launch-boundary floor)

@@ -37,13 +37,13 @@ __global__ void pack_whhT_bf16x3_kernel(const float* __restrict__ w_hh, int H, i
 }
 
 struct BwdArgs {
-  float* gd;                  // [T][B][2][NP]  in: saved gate activations; out: dL/d(pre-activation), same slots
-  const float* cs;            // [T][B][2][Hp]  cell states
-  const float* dy;            // [T][B][2][Hp]  gradient w.r.t. the layer output
-  const unsigned short* wT;   // [2][NUB][KQB][hi|lo][64][8]
-  unsigned short* ds;         // hand-off images [2 slots][2 dirs][nmt][KQB][hi|lo][64][8]
-  float* dc;                  // [2][B][Hp] carried dL/dc
-  int B, T, Hp, NP, UG, KQB, NUB, step;
+  float* gd = nullptr;                 // [T][B][2][NP]  in: saved gate activations; out: dL/d(pre-activation), same slots
+  const float* cs = nullptr;           // [T][B][2][Hp]  cell states
+  const float* dy = nullptr;           // [T][B][2][Hp]  gradient w.r.t. the layer output
+  const unsigned short* wT = nullptr;  // [2][NUB][KQB][hi|lo][64][8]
+  unsigned short* ds = nullptr;        // hand-off images [2 slots][2 dirs][nmt][KQB][hi|lo][64][8]
+  float* dc = nullptr;                 // [2][B][Hp] carried dL/dc
+  int B = 0, T = 0, Hp = 0, NP = 0, UG = 0, KQB = 0, NUB = 0, step = 0;
 };
 
 namespace recb {
@@ -247,19 +247,19 @@ __global__ __launch_bounds__(256) void lstm_pack_train_kernel(PackTrainArgs a) {
 #define ONSSEN_BWD_WIDE 1            // 1 = lstm_xcd_bwd_kernel's wide poll (RGW below) is what onssen_lstm_train_backward_* launches
 #endif
 struct XcdBwdArgs {
-  float* gd;                  // [T][B][2][NP]  in: saved gate activations; out: dL/d(pre-activation)
-  const float* cs;            // [T][B][2][Hp]
-  const float* dy;            // [T][B][2][Hp]
-  const unsigned short* wR;   // [2][NU][KC][NTB][hi|lo][64][8]
-  float* xch;                 // [8 groups][2 slots][NU dst][NU src][UG][RG] partial sums, bit 0 = tag
-  unsigned* sync;             // header words as in XcdArgs (own workspace, zeroed once by its owner)
-  int B, T, Hp, NP, NU, NTB, RG, row0, nbg;
-  unsigned spin_limit;
-  int ablate;                 // test only: 8 = rotate groups over XCDs
-  int delay;                  // s_sleep(1) repetitions between a step's stores and the first request for the next step's sums
-  long long* dbg;             // ONSSEN_XCD_PROFILE builds: 8 timestamps per step of workgroup 0 (tools/bwd_timeline.py), or null
-  float* db_rows;             // [B][2][NP] sum over t of dL/d(pre-activation) per batch row (the bias gradient is its sum over rows), or null
-  unsigned short* dp_img;     // (round 5) x3 image [T*B][2*NP/32][2][32] of dP, written INSTEAD of the fp32 dP (the gradient GEMMs' operand), or null
+  float* gd = nullptr;                 // [T][B][2][NP]  in: saved gate activations; out: dL/d(pre-activation)
+  const float* cs = nullptr;           // [T][B][2][Hp]
+  const float* dy = nullptr;           // [T][B][2][Hp]
+  const unsigned short* wR = nullptr;  // [2][NU][KC][NTB][hi|lo][64][8]
+  float* xch = nullptr;                // [8 groups][2 slots][NU dst][NU src][UG][RG] partial sums, bit 0 = tag
+  unsigned* sync = nullptr;            // header words as in XcdArgs (own workspace, zeroed once by its owner)
+  int B = 0, T = 0, Hp = 0, NP = 0, NU = 0, NTB = 0, RG = 0, row0 = 0, nbg = 0;
+  unsigned spin_limit = 0;
+  int ablate = 0;                      // test only: 8 = rotate groups over XCDs
+  int delay = 0;                       // s_sleep(1) repetitions between a step's stores and the first request for the next step's sums
+  long long* dbg = nullptr;            // ONSSEN_XCD_PROFILE builds: 8 timestamps per step of workgroup 0 (tools/bwd_timeline.py), or null
+  float* db_rows = nullptr;            // [B][2][NP] sum over t of dL/d(pre-activation) per batch row (the bias gradient is its sum over rows), or null
+  unsigned short* dp_img = nullptr;    // (round 5) x3 image [T*B][2*NP/32][2][32] of dP, written INSTEAD of the fp32 dP (the gradient GEMMs' operand), or null
 };
 
 // STACK (round 5; groups of <= 8 rows -- the as-shipped B_local = 16 runs 4-row groups): the hi and the lo half of a batch row

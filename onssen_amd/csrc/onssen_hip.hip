@@ -12,6 +12,7 @@
 //                       exchange through the XCD's L2; split-bf16 / bf16 / exact-fp32 instantiations), lstm_step_kernel (one
 //                       launch per time step: H > 640 and the re-run of an aborted call)
 //   lstm_bwd.inc        lstm_xcd_bwd_kernel / lstm_bwd_step_kernel (training: backward recurrence)
+//   lstm_run.inc        host code: the BLSTM's geometry, workspace layouts, launchers and C ABI entries (forward, pipelined pair, training)
 //   labels_cluster.inc  labels_kernel (training labels), kmeans2_* (deep-clustering back end: compaction of the active bins, all
 //                       Lloyd iterations in one persistent launch with register-resident rows; launch-per-iteration fallback)
 //   loss_sdr.inc        loss_dc_* (value and gradient) / loss_mask_* (chimera mask term: value, winning assignment, gradient),
@@ -102,12 +103,22 @@ static inline bool aligned256(const void* p) { return (reinterpret_cast<uintptr_
 #define ONSSEN_X3R_DEFAULT 0     // onssen_linear_x3p, bias mode: 1 = the 32x32x16-MFMA kernel (linear_x3r_kernel) unless ONSSEN_X3R=0 says otherwise
 #endif
 
+// Bounded waits of the persistent kernels: ~0.2 s of polling on the GPU by default.  A run-time setting of the library
+// (onssen_xcd_spin_limit), initialised from ONSSEN_XCD_SPIN_LIMIT: the host-side emulation -- where a 'workgroup' is a
+// process at the mercy of the OS scheduler -- and data-parallel training -- where a co-tenant RCCL kernel may hold CUs
+// while it waits for a slower rank -- raise it; 0 makes every wait give up at once (abort-path tests).
+static unsigned& xcd_spin_limit() {
+  static unsigned v = getenv("ONSSEN_XCD_SPIN_LIMIT") ? (unsigned)strtoul(getenv("ONSSEN_XCD_SPIN_LIMIT"), nullptr, 10) : 400000u;
+  return v;
+}
+
 // ---- device code, one translation unit (the host-side emulation compiles exactly this file too)
 #include "pack.inc"
 #include "gemm.inc"
 #include "labels_cluster.inc"
 #include "lstm.inc"
 #include "lstm_bwd.inc"
+#include "lstm_run.inc"    // BLSTM host side: geometry, workspace layouts, launchers and the C ABI entries over lstm.inc / lstm_bwd.inc
 #include "fft.inc"
 #include "loss_sdr.inc"
 #include "wav_io.inc"      // host code: the batch RIFF reader of the file loader
@@ -118,15 +129,6 @@ static inline bool aligned256(const void* p) { return (reinterpret_cast<uintptr_
 #include "tasnet_stitch.inc" // Conv-TasNet long-form separation: window gather, permutation alignment, cross-fade
 #include "tasnet_run.inc" // Conv-TasNet: the one launch sequence behind the eval, ragged, training and stream entries
 #include "loss_sisnr.inc" // Conv-TasNet training: the SI-SNR permutation-invariant loss and its gradient
-
-// Bounded waits of the persistent kernels: ~0.2 s of polling on the GPU by default.  A run-time setting of the library
-// (onssen_xcd_spin_limit), initialised from ONSSEN_XCD_SPIN_LIMIT: the host-side emulation -- where a 'workgroup' is a
-// process at the mercy of the OS scheduler -- and data-parallel training -- where a co-tenant RCCL kernel may hold CUs
-// while it waits for a slower rank -- raise it; 0 makes every wait give up at once (abort-path tests).
-static unsigned& xcd_spin_limit() {
-  static unsigned v = getenv("ONSSEN_XCD_SPIN_LIMIT") ? (unsigned)strtoul(getenv("ONSSEN_XCD_SPIN_LIMIT"), nullptr, 10) : 400000u;
-  return v;
-}
 
 // Co-tenant probe (tools/cotenant_probe.py): `workgroups` workgroups of `threads` threads that do nothing but hold their
 // CU for `ticks` ticks of the 100 MHz wall clock -- a stand-in for RCCL's channel kernels next to the persistent recurrences.
@@ -244,26 +246,6 @@ int onssen_stft_logmag_ragged_f32(const float* wav, int B, int n_max, int64_t wa
                                   int hop, float eps, float* logmag, float* stft_ri, void* stream) {
   if (!n_per_utt) return ONSSEN_E_ARG;
   return stft_logmag_impl(wav, B, n_max, wav_stride, n_fft, hop, eps, logmag, stft_ri, stream, n_per_utt);
-}
-
-int onssen_lstm_geometry(int H, int ug, int* Hp, int* NP, int* KQ, int64_t* whh_elems) {
-  if (H <= 0 || ug < 4 || ug > 24 || (ug % 4) != 0) return ONSSEN_E_ARG;
-  const int hp = ceil_div(H, ug) * ug, kq = ceil_div(hp, 16);
-  if (Hp) *Hp = hp;
-  if (NP) *NP = 4 * hp;
-  if (KQ) *KQ = kq;
-  if (whh_elems) *whh_elems = (int64_t)(hp / ug) * kq * (ug / 4) * 256;
-  return ONSSEN_OK;
-}
-
-int onssen_lstm_geometry_x3(int H, int ug, int* KQ2, int* Hs, int64_t* whh_x3_elems) {
-  int Hp;
-  if (onssen_lstm_geometry(H, ug, &Hp, nullptr, nullptr, nullptr) != ONSSEN_OK) return ONSSEN_E_ARG;
-  const int kq2 = ceil_div(Hp, 32);
-  if (KQ2) *KQ2 = kq2;
-  if (Hs) *Hs = 32 * kq2;
-  if (whh_x3_elems) *whh_x3_elems = (int64_t)(Hp / ug) * kq2 * (ug / 4) * 1024;
-  return ONSSEN_OK;
 }
 
 int onssen_lstm_pack_whh_bf16x3(const float* w_hh, int H, int ug, uint16_t* whh_x3, void* stream) {
@@ -910,390 +892,7 @@ int onssen_loss_mask_grad_f32(const float* mask_a, const float* mask_b, int64_t 
   return ONSSEN_OK;
 }
 
-
-// workspace layout: header | G | ybuf (L > 1) | c | h hand-off image | x3 images: layer-0 input, output A (the
-// LAST layer's), output B (L > 1) | 64 KiB debug
-struct BlstmWs {
-  size_t g, y, c, hs, img_x, img_y, off_imgx, off_imga, off_imgb, total;
-};
-static bool blstm_ws_layout(int B, int T, int in_dim, int H, int L, int ug, BlstmWs* w) {
-  int Hp, NP, KQ;
-  if (onssen_lstm_geometry(H, ug, &Hp, &NP, &KQ, nullptr) != ONSSEN_OK || B <= 0 || T <= 0 || L <= 0 || in_dim <= 0) return false;
-  w->g = align256((size_t)T * B * 2 * NP * sizeof(float));
-  w->y = L > 1 ? align256((size_t)T * B * 2 * Hp * sizeof(float)) : 0;
-  w->c = align256((size_t)2 * B * Hp * sizeof(float));
-  w->hs = align256((size_t)2 * 2 * ceil_div(B, 4) * ceil_div(Hp, 32) * 2048);    // h hand-off image: one per (direction, group of >= 4 rows)
-  w->img_x = align256((size_t)T * B * ceil_div(in_dim, 32) * 128);
-  w->img_y = align256((size_t)T * B * ceil_div(2 * Hp, 32) * 128);
-  w->off_imgx = ONSSEN_BLSTM_WS_HEADER_BYTES + w->g + w->y + w->c + w->hs;
-  w->off_imga = w->off_imgx + w->img_x;
-  w->off_imgb = w->off_imga + w->img_y;
-  w->total = w->off_imgb + (L > 1 ? w->img_y : 0) + 65536;   // the last 64 KiB: debug timestamps
-  return true;
-}
-
-size_t onssen_blstm_workspace_bytes(int B, int T, int in_dim, int H, int L, int ug) {
-  BlstmWs w;
-  return blstm_ws_layout(B, T, in_dim, H, L, ug, &w) ? w.total : 0;
-}
-
-int onssen_blstm_y_image(int B, int T, int in_dim, int H, int L, int ug, size_t* offset_bytes, int* KB) {
-  BlstmWs w;
-  int Hp;
-  if (!blstm_ws_layout(B, T, in_dim, H, L, ug, &w) || onssen_lstm_geometry(H, ug, &Hp, nullptr, nullptr, nullptr) != ONSSEN_OK)
-    return ONSSEN_E_ARG;
-  if (offset_bytes) *offset_bytes = w.off_imga;
-  if (KB) *KB = ceil_div(2 * Hp, 32);
-  return ONSSEN_OK;
-}
-
-int onssen_blstm_x_image(int B, int T, int in_dim, int H, int L, int ug, size_t* offset_bytes, int* KB) {
-  BlstmWs w;
-  if (!blstm_ws_layout(B, T, in_dim, H, L, ug, &w)) return ONSSEN_E_ARG;
-  if (offset_bytes) *offset_bytes = w.off_imgx;
-  if (KB) *KB = ceil_div(in_dim, 32);
-  return ONSSEN_OK;
-}
-
-// ONSSEN_BLSTM_WS_DIRTY: the k padding of a recurrence output image (columns 2*Hp .. 32*KB - 1 of every row) is never written by
-// the recurrence; a workspace that was not zeroed for this shape gets it cleared here (stale bits there could be bf16 NaNs,
-// and NaN x 0-weight = NaN in the next GEMM)
-__global__ void x3_pad_zero_kernel(unsigned short* __restrict__ img, long rows, int KB, int K) {
-  const int k0 = K & 31;                         // first padding column inside the last k block (0: no padding)
-  if (k0 == 0) return;
-  const int per = 32 - k0;
-  const long total = rows * 2 * per;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    const long row = e / (2 * per);
-    const int r = (int)(e - row * 2 * per), hl = r / per, kk = k0 + r % per;
-    img[(row * KB + (KB - 1)) * 64 + hl * 32 + kk] = 0;
-  }
-}
-
-static int blstm_forward_impl(const float* x, int64_t xs_b, int64_t xs_t, int B, int T, int in_dim, int H, int L,
-                              int ug, const float* const* wih_p_host, const float* const* whh_p_host,
-                              const float* const* bias_p_host, float* y, void* ws, size_t ws_bytes, int flags,
-                              void* stream, float* save_g, float* save_c, const int32_t* frames = nullptr) {
-  int Hp, NP, KQ;
-  int64_t we;
-  if (onssen_lstm_geometry(H, ug, &Hp, &NP, &KQ, &we) != ONSSEN_OK) return ONSSEN_E_ARG;
-  if (!x || !ws || !wih_p_host || !whh_p_host || !bias_p_host || B <= 0 || T <= 0 || in_dim <= 0 || L <= 0)
-    return ONSSEN_E_ARG;
-  // y may be NULL only in the XCD form, whose consumers can take the x3 image of the output instead
-  if (!y && !((flags & ONSSEN_BLSTM_XCD) && (flags & ONSSEN_BLSTM_BF16X3))) return ONSSEN_E_ARG;
-  // ragged batches: the persistent form exists for the plain split-bf16 inference recurrence (no fused first layer, no
-  // bf16-only products, no saved state); the launch-per-step form takes them in both precisions
-  if (frames && (flags & ONSSEN_BLSTM_XCD) &&
-      (!(flags & ONSSEN_BLSTM_BF16X3) || (flags & (ONSSEN_BLSTM_FUSE_IN0 | ONSSEN_BLSTM_BF16)) || save_g || save_c))
-    return ONSSEN_E_ARG;
-  BlstmWs wl;
-  if (!blstm_ws_layout(B, T, in_dim, H, L, ug, &wl)) return ONSSEN_E_ARG;
-  if (ws_bytes < wl.total) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(ws) & 255u) != 0 || (y && !aligned16(y))) return ONSSEN_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  char* wsp = (char*)ws;
-  unsigned* syncw = (unsigned*)wsp;
-  wsp += ONSSEN_BLSTM_WS_HEADER_BYTES;
-  float* G = (float*)wsp;
-  wsp += align256((size_t)T * B * 2 * NP * sizeof(float));
-  float* ybuf = nullptr;
-  if (L > 1) {
-    ybuf = (float*)wsp;
-    wsp += align256((size_t)T * B * 2 * Hp * sizeof(float));
-  }
-  float* cst = (float*)wsp;
-  wsp += align256((size_t)2 * B * Hp * sizeof(float));
-  const bool x3 = (flags & ONSSEN_BLSTM_BF16X3) != 0;
-  int KQ2 = 0, Hs = 0;
-  onssen_lstm_geometry_x3(H, ug, &KQ2, &Hs, nullptr);
-  if (x3 && !(flags & ONSSEN_BLSTM_XCD) && KQ2 > 4 * rec::QB3) return ONSSEN_E_ARG;   // H <= 640 in the launch-per-step split-bf16 form
-  uint16_t* hsb = (uint16_t*)wsp;
-  const size_t hs_bytes = (size_t)2 * 2 * ceil_div(B, 4) * KQ2 * 2048;   // split-bf16 images of all groups; >= the fp32 image (2*KQ2 >= KQ)
-  wsp += align256(hs_bytes);
-  long long* dbg = ((flags >> 8) & 32) && T * 8 * sizeof(long long) <= 65536 ? (long long*)((char*)ws + wl.total - 65536) : nullptr;
-  if (!(flags & ONSSEN_BLSTM_XCD)) {   // launch-per-step form: h_{-1} = 0 and the K padding of the hand-off images come from here
-    hipError_t e = hipMemsetAsync(hsb, 0, hs_bytes, st);      // (the persistent kernels clear their own slots, K padding included,
-    if (e != hipSuccess) return (int)e;                        //  before their start-up barrier: one launch less per call)
-  }
-  const int mt = (B > 16 && !(flags & ONSSEN_BLSTM_SPLIT_ROWS)) ? 2 : 1;
-  // XCD form: activations travel between the layers (and on to the heads) as x3 images written by the recurrence
-  // epilogue; wih_p_host[l] is then the x3 image of the [2*NP][K_l] input-projection matrix
-  const bool images = x3 && (flags & ONSSEN_BLSTM_XCD);
-  const bool bf16_only = images && (flags & ONSSEN_BLSTM_BF16);   // plain bf16 products instead of the three-term split
-  uint16_t* img_x = (uint16_t*)((char*)ws + wl.off_imgx);
-  uint16_t* img_ab[2] = {(uint16_t*)((char*)ws + wl.off_imga), (uint16_t*)((char*)ws + wl.off_imgb)};
-  if (images && (flags & ONSSEN_BLSTM_WS_DIRTY) && ((2 * Hp) & 31)) {
-    const long rows = (long)T * B;
-    const long n = rows * 2 * (32 - ((2 * Hp) & 31));
-    const unsigned nb = (unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-    for (int i = 0; i < (L > 1 ? 2 : 1); ++i)
-      hipLaunchKernelGGL(x3_pad_zero_kernel, dim3(nb), dim3(256), 0, st, img_ab[i], rows, ceil_div(2 * Hp, 32), 2 * Hp);
-  }
-  for (int l = 0; l < L; ++l) {
-    // the last layer writes `y`; the layers before it alternate so that each reads what the previous wrote
-    float* yout = ((L - 1 - l) % 2 == 0) ? y : ybuf;
-    const float* yin = ((L - 1 - l) % 2 == 0) ? ybuf : y;
-    int rc;
-    const bool fuse0 = images && l == 0 && (flags & ONSSEN_BLSTM_FUSE_IN0);
-    // the fused projection keeps <= 4 k-chunks of W_ih fragments in the LDS: in_dim <= 128, or 32k + 1 <= 129 with FUSE_TAIL
-    if (fuse0 && !(in_dim <= 128 || (in_dim == 129 && (flags & ONSSEN_BLSTM_FUSE_TAIL)))) return ONSSEN_E_ARG;
-    if ((flags & ONSSEN_BLSTM_G_READY) && !fuse0) {
-      rc = ONSSEN_OK;              // profiling: G of this layer is what an earlier call left in the workspace
-    } else if (images) {
-      const uint16_t* a_img = l == 0 ? img_x : img_ab[(L - l) % 2];   // layer l-1 wrote buffer (L-1-(l-1)) % 2
-      if (l == 0) {
-        rc = onssen_x3_image_f32(x, xs_t, xs_b, B, T * B, in_dim, img_x, stream);
-        if (rc != ONSSEN_OK) return rc;
-      }
-      if (fuse0) rc = ONSSEN_OK;   // x_t W_ih^T is computed inside the recurrence launch: no G, no GEMM
-      else rc = onssen_linear_x3p(a_img, T * B, l == 0 ? in_dim : 2 * Hp, (const uint16_t*)wih_p_host[l], bias_p_host[l],
-                             2 * NP, ONSSEN_EPI_BIAS | (bf16_only ? ONSSEN_EPI_BF16 : 0), 0, 0.f, G, B, (int64_t)B * 2 * NP, 2 * NP, stream);
-    } else if (x3) {   // wih_p_host[l]: split-bf16 planes [2][2*NP][ld], ld = K rounded up to 32
-      const int K = l == 0 ? in_dim : 2 * Hp, ld = ceil_div(K, 32) * 32;
-      rc = onssen_linear_bf16x3(l == 0 ? x : yin, l == 0 ? xs_t : (int64_t)B * 2 * Hp, l == 0 ? xs_b : 2 * Hp, B, T * B,
-                                K, (const uint16_t*)wih_p_host[l], ld, bias_p_host[l], 2 * NP, ONSSEN_EPI_BIAS, 0, 0.f,
-                                nullptr, G, (int64_t)B * 2 * NP, 2 * NP, stream);
-    } else if (l == 0) {
-      const int Kp = ceil_div(in_dim, 4) * 4;
-      rc = onssen_linear_f32(x, xs_t, xs_b, B, T * B, in_dim, wih_p_host[0], Kp, bias_p_host[0], 2 * NP,
-                             ONSSEN_EPI_BIAS, 0, 0.f, nullptr, G, (int64_t)B * 2 * NP, 2 * NP, stream);
-    } else {
-      rc = onssen_linear_f32(yin, (int64_t)B * 2 * Hp, 2 * Hp, B, T * B, 2 * Hp, wih_p_host[l], 2 * Hp,
-                             bias_p_host[l], 2 * NP, ONSSEN_EPI_BIAS, 0, 0.f, nullptr, G, (int64_t)B * 2 * NP,
-                             2 * NP, stream);
-    }
-    if (rc != ONSSEN_OK) return rc;
-    if (flags & ONSSEN_BLSTM_XCD) {
-      // without ONSSEN_BLSTM_BF16X3: the exact-fp32 instantiation (whh_p_host[l] = the fp32 fragment image of
-      // onssen_lstm_pack_f32, G from the exact-fp32 GEMM above, fp32 rows between the layers)
-      // split-bf16: H <= 768 (ug = 24: 32 members of 24 units = every CU of an XCD; round 4), exact fp32 and the forms that fuse
-      // the first layer / save state: H <= 640 (ug <= 20)
-      if (ug > 24 || Hp / ug > 32 || KQ2 > 24 || (!x3 && (save_g || save_c))) return ONSSEN_E_ARG;
-      if (ug > 20 && (!x3 || fuse0 || (flags & ONSSEN_BLSTM_BF16))) return ONSSEN_E_ARG;
-      // bounded waits: ~0.2 s of polling on the GPU; ONSSEN_XCD_SPIN_LIMIT overrides (the host-side emulation, where a
-      // 'workgroup' is a process at the mercy of the OS scheduler, raises it)
-      const unsigned xcd_spin = xcd_spin_limit();
-      XcdArgs xa;
-      // fp32 rows only where somebody reads them (the caller's y); every layer leaves its x3 image
-      xa.G = G; xa.whh = (const unsigned short*)whh_p_host[l]; xa.y = x3 ? (l == L - 1 ? y : nullptr) : yout; xa.hx = hsb; xa.sync = syncw; xa.B = B;
-      xa.yimg = x3 ? img_ab[(L - 1 - l) % 2] : nullptr; xa.KBI = ceil_div(2 * Hp, 32);
-      xa.wih0 = fuse0 ? (const unsigned short*)wih_p_host[0] : nullptr; xa.ximg = img_x; xa.bias0 = bias_p_host[0];
-      xa.KC0 = fuse0 ? ceil_div(in_dim, 32) : 0;
-      // in_dim = 32k + 1 (F = 129): the lone last column goes to the VALU; its weights follow the bias (FUSE_TAIL)
-      const bool vtail = fuse0 && (flags & ONSSEN_BLSTM_FUSE_TAIL) && (in_dim % 32) == 1 && in_dim > 1;
-      xa.KCM = vtail ? xa.KC0 - 1 : xa.KC0; xa.x0 = x; xa.xs_b = (long)xs_b; xa.xs_t = (long)xs_t;
-      xa.wtail = vtail ? bias_p_host[0] + 2 * NP : nullptr;
-      xa.T = T; xa.Hp = Hp; xa.NP = NP; xa.KQ2 = KQ2; xa.NU = Hp / ug; xa.row0 = 0; xa.nbg = 0; xa.spin_limit = xcd_spin; xa.dbg = dbg; xa.ablate = (flags >> 8) & 8;
-      xa.terms = !x3 ? 0 : bf16_only ? 1 : 3;
-      xa.save_g = save_g; xa.save_c = save_c;
-      xa.frames = frames;
-      ONSSEN_CLEAR_ERROR();
-      // waves per workgroup (K is split over them): 8 = two per SIMD; ONSSEN_XCD_WAVES=4 keeps the one-per-SIMD form for comparison
-      static const int xcd_nw = ONSSEN_KNOB_INT("ONSSEN_XCD_WAVES", 8) == 4 ? 4 : 8;
-      switch (ug) {
-        case 4: rc = launch_xcd<1>(xa, xcd_nw, st); break;
-        case 8: rc = launch_xcd<2>(xa, xcd_nw, st); break;
-        case 12: rc = launch_xcd<3>(xa, xcd_nw, st); break;
-        case 16: rc = launch_xcd<4>(xa, xcd_nw, st); break;
-        case 20: rc = launch_xcd<5>(xa, xcd_nw, st); break;
-        default: rc = launch_xcd_wide(xa, st); break;      // ug = 24: 640 < H <= 768
-      }
-      if (rc != ONSSEN_OK) return rc;
-      continue;
-    }
-    StepArgs sp;
-    sp.G = G; sp.whh = x3 ? nullptr : whh_p_host[l]; sp.whh_x3 = x3 ? (const unsigned short*)whh_p_host[l] : nullptr;
-    sp.hs = hsb; sp.KQ2 = KQ2; sp.Hs = Hs; sp.dbg = dbg; sp.y = yout; sp.c = cst; sp.B = B; sp.T = T; sp.Hp = Hp; sp.NP = NP;
-    sp.KQ = KQ; sp.NU = Hp / ug; sp.step = 0; sp.ablate = (flags >> 8) & 63; sp.frames = frames;
-    sp.save_g = save_g; sp.save_c = save_c;
-#define ONSSEN_STEPS(MT_, NT_) rc = launch_steps<MT_, NT_>(sp, (char*)ws, T, x3, st)
-    if (mt == 1) {
-      switch (ug) {
-        case 4: ONSSEN_STEPS(1, 1); break;
-        case 8: ONSSEN_STEPS(1, 2); break;
-        case 12: ONSSEN_STEPS(1, 3); break;
-        case 16: ONSSEN_STEPS(1, 4); break;
-        default: ONSSEN_STEPS(1, 5); break;
-      }
-    } else {
-      switch (ug) {
-        case 4: ONSSEN_STEPS(2, 1); break;
-        case 8: ONSSEN_STEPS(2, 2); break;
-        case 12: ONSSEN_STEPS(2, 3); break;
-        case 16: ONSSEN_STEPS(2, 4); break;
-        default: ONSSEN_STEPS(2, 5); break;
-      }
-    }
-#undef ONSSEN_STEPS
-    if (rc != ONSSEN_OK) return rc;
-  }
-  return ONSSEN_OK;
-}
-
-int onssen_blstm_forward_f32(const float* x, int64_t xs_b, int64_t xs_t, int B, int T, int in_dim, int H, int L,
-                             int ug, const float* const* wih_p_host, const float* const* whh_p_host,
-                             const float* const* bias_p_host, float* y, void* ws, size_t ws_bytes, int flags,
-                             void* stream) {
-  return blstm_forward_impl(x, xs_b, xs_t, B, T, in_dim, H, L, ug, wih_p_host, whh_p_host, bias_p_host, y, ws, ws_bytes,
-                            flags, stream, nullptr, nullptr);
-}
-
-int onssen_blstm_forward_ragged_f32(const float* x, int64_t xs_b, int64_t xs_t, int B, int T, const int32_t* frames,
-                                    int in_dim, int H, int L, int ug, const float* const* wih_p_host,
-                                    const float* const* whh_p_host, const float* const* bias_p_host, float* y, void* ws,
-                                    size_t ws_bytes, int flags, void* stream) {
-  if (!frames) return ONSSEN_E_ARG;
-  return blstm_forward_impl(x, xs_b, xs_t, B, T, in_dim, H, L, ug, wih_p_host, whh_p_host, bias_p_host, y, ws, ws_bytes,
-                            flags, stream, nullptr, nullptr, frames);
-}
-
-// ---- two-layer stack, software-pipelined over consecutive calls (round 6) -------------------------------------------
-// workspace: header | G0 | G1 | h hand-off images of 8 groups | x3 images: input, layer-0 output, layer-1 output | 64 KiB debug
-struct Pipe2Ws {
-  size_t g, hs, img_x, img_y, off_g0, off_g1, off_hs, off_imgx, off_img0, off_img1, total;
-};
-static bool pipe2_ws_layout(int B, int T, int in_dim, int H, int ug, Pipe2Ws* w) {
-  int Hp, NP, KQ2 = 0, Hs = 0;
-  if (onssen_lstm_geometry(H, ug, &Hp, &NP, nullptr, nullptr) != ONSSEN_OK || B <= 0 || B > 32 || T <= 0 || in_dim <= 0) return false;
-  if (onssen_lstm_geometry_x3(H, ug, &KQ2, &Hs, nullptr) != ONSSEN_OK) return false;
-  w->g = align256((size_t)T * B * 2 * NP * sizeof(float));
-  w->hs = align256((size_t)8 * 2 * KQ2 * 2048);                 // 8 groups x 2 slots x KQ2 chunks of 2 KiB
-  w->img_x = align256((size_t)T * B * ceil_div(in_dim, 32) * 128);
-  w->img_y = align256((size_t)T * B * ceil_div(2 * Hp, 32) * 128);
-  w->off_g0 = ONSSEN_BLSTM_WS_HEADER_BYTES;
-  w->off_g1 = w->off_g0 + w->g;
-  w->off_hs = w->off_g1 + w->g;
-  w->off_imgx = w->off_hs + w->hs;
-  w->off_img0 = w->off_imgx + w->img_x;
-  w->off_img1 = w->off_img0 + w->img_y;
-  w->total = w->off_img1 + w->img_y + 65536;
-  return true;
-}
-
-size_t onssen_blstm_pipe2_workspace_bytes(int B, int T, int in_dim, int H, int ug) {
-  Pipe2Ws w;
-  return pipe2_ws_layout(B, T, in_dim, H, ug, &w) ? w.total : 0;
-}
-
-int onssen_blstm_pipe2_y_image(int B, int T, int in_dim, int H, int ug, size_t* offset_bytes, int* KB) {
-  Pipe2Ws w;
-  int Hp;
-  if (!pipe2_ws_layout(B, T, in_dim, H, ug, &w) || onssen_lstm_geometry(H, ug, &Hp, nullptr, nullptr, nullptr) != ONSSEN_OK)
-    return ONSSEN_E_ARG;
-  if (offset_bytes) *offset_bytes = w.off_img1;
-  if (KB) *KB = ceil_div(2 * Hp, 32);
-  return ONSSEN_OK;
-}
-
-// T_cap lays the workspace out (>= every T that passes through it); the uniform form has T_cap = T = T_prev and no frames
-static int blstm_pipe2_impl(const float* x, int64_t xs_b, int64_t xs_t, int B, int T_cap, int T, const int32_t* frames, int T_prev,
-                            const int32_t* frames_prev, int in_dim, int H, int ug, const float* const* wih_p_host,
-                            const float* const* whh_p_host, const float* const* bias_p_host, void* ws, size_t ws_bytes, int flags,
-                            void* stream) {
-  int Hp, NP, KQ2 = 0, Hs = 0;
-  if (onssen_lstm_geometry(H, ug, &Hp, &NP, nullptr, nullptr) != ONSSEN_OK) return ONSSEN_E_ARG;
-  if (!x || !ws || !wih_p_host || !whh_p_host || !bias_p_host || B <= 0 || B > 32 || T <= 0 || in_dim <= 0) return ONSSEN_E_ARG;
-  if (T > T_cap || T_prev <= 0 || T_prev > T_cap) return ONSSEN_E_ARG;
-  // ragged rows keep the bits of their own batch-1 run: stacked tiles only, i.e. <= 16 rows; both batches bring their frames
-  if ((frames != nullptr) != (frames_prev != nullptr) || (frames && B > 16)) return ONSSEN_E_ARG;
-  // the plain split-bf16 persistent recurrence only (no fused first layer, no bf16-only products)
-  if ((flags & 0xff & ~ONSSEN_BLSTM_G_READY) != (ONSSEN_BLSTM_BF16X3 | ONSSEN_BLSTM_XCD)) return ONSSEN_E_ARG;
-  const bool g_ready = (flags & ONSSEN_BLSTM_G_READY) != 0;     // measurement aid: the pair launch by itself, on the projections an earlier call left
-  Pipe2Ws wl;
-  if (!pipe2_ws_layout(B, T_cap, in_dim, H, ug, &wl)) return ONSSEN_E_ARG;
-  if (ws_bytes < wl.total) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(ws) & 255u) != 0) return ONSSEN_E_ALIGN;
-  onssen_lstm_geometry_x3(H, ug, &KQ2, &Hs, nullptr);
-  if (ug > 20 || Hp / ug > 32 || KQ2 > 24) return ONSSEN_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)ws;
-  float* G0 = (float*)(base + wl.off_g0);
-  float* G1 = (float*)(base + wl.off_g1);
-  uint16_t* img_x = (uint16_t*)(base + wl.off_imgx);
-  uint16_t* img0 = (uint16_t*)(base + wl.off_img0);
-  uint16_t* img1 = (uint16_t*)(base + wl.off_img1);
-  // layer 0 of THIS batch: input image, input projection
-  int rc = ONSSEN_OK;
-  if (!g_ready) {
-    rc = onssen_x3_image_f32(x, xs_t, xs_b, B, T * B, in_dim, img_x, stream);
-    if (rc != ONSSEN_OK) return rc;
-    rc = onssen_linear_x3p(img_x, T * B, in_dim, (const uint16_t*)wih_p_host[0], bias_p_host[0], 2 * NP, ONSSEN_EPI_BIAS, 0, 0.f, G0, B,
-                           (int64_t)B * 2 * NP, 2 * NP, stream);
-    if (rc != ONSSEN_OK) return rc;
-  }
-  // ONE launch: layer 1 of the batch before (its G1 was left by the call before) beside layer 0 of this one
-  XcdArgs xa;
-  xa.G = G1; xa.whh = (const unsigned short*)whh_p_host[1]; xa.y = nullptr; xa.yimg = img1;
-  xa.G_b = G0; xa.whh_b = (const unsigned short*)whh_p_host[0]; xa.yimg_b = img0;
-  xa.hx = (unsigned short*)(base + wl.off_hs); xa.sync = (unsigned*)base; xa.B = B; xa.KBI = ceil_div(2 * Hp, 32);
-  xa.wih0 = nullptr; xa.ximg = img_x; xa.bias0 = bias_p_host[0]; xa.KC0 = 0; xa.KCM = 0; xa.x0 = x; xa.xs_b = (long)xs_b; xa.xs_t = (long)xs_t;
-  xa.wtail = nullptr;
-  xa.T = T_prev; xa.T_b = T; xa.frames = frames_prev; xa.frames_b = frames;
-  xa.Hp = Hp; xa.NP = NP; xa.KQ2 = KQ2; xa.NU = Hp / ug; xa.row0 = 0; xa.nbg = 0; xa.spin_limit = xcd_spin_limit();
-  xa.dbg = nullptr; xa.ablate = (flags >> 8) & 8; xa.terms = 3; xa.save_g = nullptr; xa.save_c = nullptr;
-  ONSSEN_CLEAR_ERROR();
-  switch (ug) {
-    case 4: rc = launch_xcd_pair<1>(xa, st); break;
-    case 8: rc = launch_xcd_pair<2>(xa, st); break;
-    case 12: rc = launch_xcd_pair<3>(xa, st); break;
-    case 16: rc = launch_xcd_pair<4>(xa, st); break;
-    case 20: rc = launch_xcd_pair<5>(xa, st); break;
-    default: return ONSSEN_E_ARG;
-  }
-  if (rc != ONSSEN_OK || g_ready) return rc;
-  // layer 1's input projection of THIS batch, for the next call
-  return onssen_linear_x3p(img0, T * B, 2 * Hp, (const uint16_t*)wih_p_host[1], bias_p_host[1], 2 * NP, ONSSEN_EPI_BIAS, 0, 0.f, G1, B,
-                           (int64_t)B * 2 * NP, 2 * NP, stream);
-}
-
-int onssen_blstm_pipe2_forward_f32(const float* x, int64_t xs_b, int64_t xs_t, int B, int T, int in_dim, int H, int ug,
-                                   const float* const* wih_p_host, const float* const* whh_p_host,
-                                   const float* const* bias_p_host, void* ws, size_t ws_bytes, int flags, void* stream) {
-  return blstm_pipe2_impl(x, xs_b, xs_t, B, T, T, nullptr, T, nullptr, in_dim, H, ug, wih_p_host, whh_p_host, bias_p_host, ws, ws_bytes,
-                          flags, stream);
-}
-
-int onssen_blstm_pipe2_forward_ragged_f32(const float* x, int64_t xs_b, int64_t xs_t, int B, int T_cap, int T, const int32_t* frames,
-                                          int T_prev, const int32_t* frames_prev, int in_dim, int H, int ug,
-                                          const float* const* wih_p_host, const float* const* whh_p_host,
-                                          const float* const* bias_p_host, void* ws, size_t ws_bytes, int flags, void* stream) {
-  if (!frames || !frames_prev) return ONSSEN_E_ARG;
-  return blstm_pipe2_impl(x, xs_b, xs_t, B, T_cap, T, frames, T_prev, frames_prev, in_dim, H, ug, wih_p_host, whh_p_host, bias_p_host, ws,
-                          ws_bytes, flags, stream);
-}
-
-// ---- training: one layer forward with saved state, and its backward recurrence ----------------
-int onssen_lstm_train_forward_f32(const float* x, int64_t xs_b, int64_t xs_t, int B, int T, int in_dim, int H, int ug,
-                                  const uint16_t* wih_img, const uint16_t* whh_x3, const float* bias_p, float* y,
-                                  float* gates, float* cs, void* ws, size_t ws_bytes, void* stream) {
-  if (!y || !gates || !cs || !aligned16(gates)) return ONSSEN_E_ARG;
-  const float* wih[1] = {(const float*)wih_img};
-  const float* whh[1] = {(const float*)whh_x3};
-  const float* bias[1] = {bias_p};
-  return blstm_forward_impl(x, xs_b, xs_t, B, T, in_dim, H, 1, ug, wih, whh, bias, y, ws, ws_bytes,
-                            ONSSEN_BLSTM_BF16X3 | ONSSEN_BLSTM_XCD, stream, gates, cs);
-}
-
-static bool lstm_bwd_geometry(int H, int ug, int* Hp, int* NP, int* KQB, int* NUB) {
-  if (onssen_lstm_geometry(H, ug, Hp, NP, nullptr, nullptr) != ONSSEN_OK) return false;
-  *KQB = ceil_div(*NP, 32);
-  *NUB = ceil_div(*Hp, 16);
-  return true;
-}
-
-int onssen_lstm_train_forward_form_f32(const float* x, int64_t xs_b, int64_t xs_t, int B, int T, int in_dim, int H, int ug,
-                                       const void* wih, const void* whh, const float* bias_p, float* y, float* gates,
-                                       float* cs, void* ws, size_t ws_bytes, int flags, void* stream) {
-  if (!y || !gates || !cs || !aligned16(gates)) return ONSSEN_E_ARG;
-  // the forms that can save state: the persistent split-bf16 launch, and the launch-per-step recurrence in either precision
-  const int form = flags & (ONSSEN_BLSTM_XCD | ONSSEN_BLSTM_BF16X3);
-  if ((flags & ~(ONSSEN_BLSTM_XCD | ONSSEN_BLSTM_BF16X3)) != 0 || form == ONSSEN_BLSTM_XCD) return ONSSEN_E_ARG;
-  const float* wih_a[1] = {(const float*)wih};
-  const float* whh_a[1] = {(const float*)whh};
-  const float* bias[1] = {bias_p};
-  return blstm_forward_impl(x, xs_b, xs_t, B, T, in_dim, H, 1, ug, wih_a, whh_a, bias, y, ws, ws_bytes, flags, stream, gates, cs);
-}
-
+// ---- training: weight images for the backward recurrence (the training forward and the backward itself: lstm_run.inc) ----
 int64_t onssen_lstm_whhT_elems(int H, int ug) {
   int Hp, NP, KQB, NUB;
   if (!lstm_bwd_geometry(H, ug, &Hp, &NP, &KQB, &NUB)) return 0;
@@ -1370,115 +969,6 @@ int onssen_lstm_pack_train_f32(int L, int in_dim, int H, int ug, const float* co
       }
     }
     hipLaunchKernelGGL(lstm_pack_train_kernel, dim3((unsigned)fb), dim3(256), 0, (hipStream_t)stream, a);
-  }
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-static int bwd_rows_per_group(int B) {
-  int rg = B <= 16 ? 4 : B <= 32 ? 8 : 16;
-  static const int rg_env = ONSSEN_KNOB_INT("ONSSEN_XCD_RG", 0);
-  if (rg_env == 4 || rg_env == 8 || rg_env == 16) rg = rg_env;
-  return rg;
-}
-
-size_t onssen_lstm_train_backward_workspace_bytes(int B, int H, int ug, int form) {
-  int Hp, NP, KQB, NUB;
-  if (B <= 0 || !lstm_bwd_geometry(H, ug, &Hp, &NP, &KQB, &NUB)) return 0;
-  if (form == ONSSEN_LSTM_BWD_XCD) {
-    const int NU = Hp / ug, RG = bwd_rows_per_group(B);
-    return ONSSEN_BLSTM_WS_HEADER_BYTES + align256((size_t)8 * 2 * NU * NU * RG * ug * sizeof(float));
-  }
-  return align256((size_t)2 * 2 * ceil_div(B, 16) * KQB * 2048) + align256((size_t)2 * B * Hp * sizeof(float));
-}
-
-static int lstm_train_backward_impl(int B, int T, int H, int ug, const uint16_t* whh_img, const float* dy, float* gates_dp,
-                                    const float* cs, void* ws, size_t ws_bytes, int form, float* db_rows, uint16_t* dp_img, void* stream);
-
-int onssen_lstm_train_backward_f32(int B, int T, int H, int ug, const uint16_t* whh_img, const float* dy, float* gates_dp,
-                                   const float* cs, void* ws, size_t ws_bytes, int form, float* db_rows, void* stream) {
-  return lstm_train_backward_impl(B, T, H, ug, whh_img, dy, gates_dp, cs, ws, ws_bytes, form, db_rows, nullptr, stream);
-}
-
-int onssen_lstm_train_backward_img_f32(int B, int T, int H, int ug, const uint16_t* whh_img, const float* dy, const float* gates,
-                                       const float* cs, void* ws, size_t ws_bytes, float* db_rows, uint16_t* dp_img, void* stream) {
-  int Hp, NP;
-  if (!dp_img || !aligned16(dp_img) || onssen_lstm_geometry(H, ug, &Hp, &NP, nullptr, nullptr) != ONSSEN_OK || (2 * NP) % 32 != 0)
-    return ONSSEN_E_ARG;
-  return lstm_train_backward_impl(B, T, H, ug, whh_img, dy, const_cast<float*>(gates), cs, ws, ws_bytes, ONSSEN_LSTM_BWD_XCD, db_rows,
-                                  dp_img, stream);
-}
-
-static int lstm_train_backward_impl(int B, int T, int H, int ug, const uint16_t* whh_img, const float* dy, float* gates_dp,
-                                    const float* cs, void* ws, size_t ws_bytes, int form, float* db_rows, uint16_t* dp_img, void* stream) {
-  int Hp, NP, KQB, NUB;
-  if (!whh_img || !dy || !gates_dp || !cs || !ws || B <= 0 || T <= 0 || !lstm_bwd_geometry(H, ug, &Hp, &NP, &KQB, &NUB) ||
-      (form != ONSSEN_LSTM_BWD_STEPS && form != ONSSEN_LSTM_BWD_XCD) || (db_rows && form != ONSSEN_LSTM_BWD_XCD) ||
-      (db_rows && !aligned16(db_rows)))
-    return ONSSEN_E_ARG;
-  if (ws_bytes < onssen_lstm_train_backward_workspace_bytes(B, H, ug, form)) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(ws) & 255u) != 0 || !aligned16(gates_dp)) return ONSSEN_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (form == ONSSEN_LSTM_BWD_XCD) {
-    if (Hp / ug > 32 || NUB > 40) return ONSSEN_E_ARG;
-    const unsigned xcd_spin = xcd_spin_limit();
-    static const int ablate_env = ONSSEN_KNOB_INT("ONSSEN_BWD_ABLATE", 0);
-    static const int delay_env = ONSSEN_KNOB_INT("ONSSEN_BWD_DELAY", 0);
-    static const bool bwd_unstacked = ONSSEN_KNOB_INT("ONSSEN_BWD_UNSTACKED", 0) != 0;      // debug builds: the three-term form of rounds 2-4, for A/B
-    static const bool bwd_wide = ONSSEN_KNOB_INT("ONSSEN_BWD_WIDE", ONSSEN_BWD_WIDE) != 0;      // the wide poll of round 6 (lstm_bwd.inc: RGW)
-    XcdBwdArgs xa;
-    xa.gd = gates_dp; xa.cs = cs; xa.dy = dy; xa.wR = whh_img; xa.sync = (unsigned*)ws;
-    xa.xch = (float*)((char*)ws + ONSSEN_BLSTM_WS_HEADER_BYTES);
-    xa.B = B; xa.T = T; xa.Hp = Hp; xa.NP = NP; xa.NU = Hp / ug; xa.NTB = NUB; xa.RG = bwd_rows_per_group(B);
-    xa.spin_limit = xcd_spin; xa.ablate = ablate_env; xa.delay = delay_env; xa.db_rows = db_rows; xa.dp_img = dp_img;
-    // ONSSEN_XCD_PROFILE builds only (ONSSEN_BWD_DBG=1, tools/bwd_timeline.py): 8 timestamps per step of workgroup 0 in the tail of ws
-    static const bool dbg_env = ONSSEN_KNOB_INT("ONSSEN_BWD_DBG", 0) != 0;
-    xa.dbg = dbg_env && ws_bytes >= onssen_lstm_train_backward_workspace_bytes(B, H, ug, form) + (size_t)T * 64
-                 ? (long long*)((char*)ws + onssen_lstm_train_backward_workspace_bytes(B, H, ug, form)) : nullptr;
-    ONSSEN_CLEAR_ERROR();
-    const dim3 grid((unsigned)(8 * xa.NU));
-    const int E = xa.RG * ug, parts = 4 * E <= 320 ? 4 : 2 * E <= 320 ? 2 : 1;   // polling lanes per element (320 polling threads)
-    for (int r0 = 0; r0 < B; r0 += 4 * xa.RG) {
-      const int rows = B - r0 < 4 * xa.RG ? B - r0 : 4 * xa.RG;
-      xa.row0 = r0;
-      xa.nbg = ceil_div(rows, xa.RG);
-#define ONSSEN_BWD_UG(UG_)                                                                                   \
-  do {                                                                                                       \
-    if (bwd_wide && !bwd_unstacked) {   /* round 6: the wide poll (16-byte loads, 16 lanes per unit) */       \
-      if (xa.RG == 4) hipLaunchKernelGGL((lstm_xcd_bwd_kernel<UG_, 1, true, 4>), grid, dim3(512), 0, st, xa);  \
-      else if (xa.RG == 8) hipLaunchKernelGGL((lstm_xcd_bwd_kernel<UG_, 1, true, 8>), grid, dim3(512), 0, st, xa); \
-      else hipLaunchKernelGGL((lstm_xcd_bwd_kernel<UG_, 1, false, 16>), grid, dim3(512), 0, st, xa);          \
-    } else if (xa.RG <= 8 && !bwd_unstacked) {                                                               \
-      if (parts == 4) hipLaunchKernelGGL((lstm_xcd_bwd_kernel<UG_, 4, true>), grid, dim3(512), 0, st, xa);     \
-      else if (parts == 2) hipLaunchKernelGGL((lstm_xcd_bwd_kernel<UG_, 2, true>), grid, dim3(512), 0, st, xa);\
-      else hipLaunchKernelGGL((lstm_xcd_bwd_kernel<UG_, 1, true>), grid, dim3(512), 0, st, xa);                \
-    } else if (parts == 4) hipLaunchKernelGGL((lstm_xcd_bwd_kernel<UG_, 4, false>), grid, dim3(512), 0, st, xa); \
-    else if (parts == 2) hipLaunchKernelGGL((lstm_xcd_bwd_kernel<UG_, 2, false>), grid, dim3(512), 0, st, xa); \
-    else hipLaunchKernelGGL((lstm_xcd_bwd_kernel<UG_, 1, false>), grid, dim3(512), 0, st, xa);                 \
-  } while (0)
-      switch (ug) {
-        case 4: ONSSEN_BWD_UG(4); break;
-        case 8: ONSSEN_BWD_UG(8); break;
-        case 12: ONSSEN_BWD_UG(12); break;
-        case 16: ONSSEN_BWD_UG(16); break;
-        default: ONSSEN_BWD_UG(20); break;
-      }
-#undef ONSSEN_BWD_UG
-    }
-    ONSSEN_LAUNCH_CHECK();
-    return ONSSEN_OK;
-  }
-  const size_t img_bytes = align256((size_t)2 * 2 * ceil_div(B, 16) * KQB * 2048);
-  hipError_t e = hipMemsetAsync(ws, 0, img_bytes, st);   // rows past B and the K tail of the images stay zero
-  if (e != hipSuccess) return (int)e;
-  BwdArgs p;
-  p.gd = gates_dp; p.cs = cs; p.dy = dy; p.wT = whh_img; p.ds = (unsigned short*)ws; p.dc = (float*)((char*)ws + img_bytes);
-  p.B = B; p.T = T; p.Hp = Hp; p.NP = NP; p.UG = ug; p.KQB = KQB; p.NUB = NUB;
-  ONSSEN_CLEAR_ERROR();
-  const dim3 grid((unsigned)NUB, 2, (unsigned)ceil_div(B, 16));
-  for (int s = 0; s < T; ++s) {
-    p.step = s;
-    hipLaunchKernelGGL(lstm_bwd_step_kernel, grid, dim3(64 * recb::NW), 0, st, p);
   }
   ONSSEN_LAUNCH_CHECK();
   return ONSSEN_OK;

@@ -28,7 +28,7 @@ d = ws[nb - 65536:].cpu().numpy().view(np.int64)[:STN * 24].reshape(STN, 24)[2:S
 per = (d[1:, 0] - d[:-1, 0]).mean()
 m = lambda a, b: (d[:, a] - d[:, b]).mean()
 st = ws[:2048].cpu().numpy().view(np.uint32)
-print(f"ablate={AB} B={B} ug={ug} waves={os.environ.get('ONSSEN_XCD_WAVES', 8)}: cycles/step {per:.0f} | wave 0: step start->all chunks complete {m(8,0):.0f} | "
+print(f"ablate={AB} B={B} ug={ug}: cycles/step {per:.0f} | wave 0: step start->all chunks complete {m(8,0):.0f} | "
       f"MFMA {m(7,8):.0f} | partials written {m(2,7):.0f} | barrier {m(3,2):.0f} | G prefetch + cell update + hand-off stores issued {m(4,3):.0f} | "
       f"output stores + pause {m(6,4):.0f} | next chunks requested {m(5,6):.0f} | to next step {(d[1:, 0] - d[:-1, 5]).mean():.0f} | abort={st[280]} safe={st[281]} nonfinite={st[282]}"
       f" || cell update of wave 0: barrier -> sums in registers {m(16,3):.0f} | gates + cell + h {m(17,16):.0f} | split + quad gather {m(18,17):.0f} | hand-off store issued {m(19,18):.0f} | done counter {m(4,19):.0f}"
