@@ -546,6 +546,31 @@ int onssen_loss_mask_grad_f32(const float* mask_a, const float* mask_b, int64_t 
                               const float* mag_s1, const float* mag_s2, const float* cos_s1, const float* cos_s2, int B, int TF,
                               const float* g, const int32_t* perm, float* d_mask_a, float* d_mask_b, int64_t d_sb, int64_t d_se,
                               void* stream);
+/* Mask term and phase term of phase_net's training loss (onssen/loss/loss_phase.py:15-35, with its strict comparison), one
+ * pass over the eleven maps.  Masks, mag_mix, mag_s* as above; phase_a, phase_b (the estimates) and phase_s1, phase_s2 (the
+ * targets: raw (Re, Im) STFT values, exactly 0 in silent bins) are (B, TF, 2), contiguous and 8-byte aligned.  eps = 1e-8:
+ *   l1 = sum |mA x - s1| + sum |mB x - s2|,  l2 = sum |mB x - s1| + sum |mA x - s2|,
+ *   cos(p, q) = <p / max(|p|, eps), q / max(|q|, eps)>                      (F.cosine_similarity: each norm clamped)
+ *   perm[b] = 0 (A->1, B->2) if and only if l1 < l2, else 1 (A->2, B->1): a tie is SWAPPED, unlike onssen_loss_mask_f32
+ *   out_mask[b] = the chosen l,  out_phase[b] = -sum mag_mix (cos(pA, q_A) + cos(pB, q_B)) under the same assignment.
+ * Per-bin terms in fp32, sums in fp64 in a fixed order (no atomics: bit-repeatable).  ws: caller-owned, 8-byte aligned,
+ * onssen_loss_phase_workspace_bytes bytes, needs no zeroing.
+ * onssen_loss_phase_grad_f32, one elementwise pass under `perm`:
+ *   d_mask_A[b,e]  = g_mask[b] * mag_mix * sign(mask_A * mag_mix - s_A)     (as onssen_loss_mask_grad_f32; strided by d_sb, d_se)
+ *   d_phase_A[b,e] = -g_phase[b] * mag_mix * (q^ - c p^) / N,  N = max(|p|, eps), c = <p / N, q^>, p^ = p / |p| (0 at p = 0),
+ *                    q^ = q / max(|q|, eps): what autograd derives from F.cosine_similarity (the norm's value is clamped, its
+ *                    derivative is not); a zero target gives 0.
+ *   d_phase_* (B, TF, 2) contiguous, 8-byte aligned. */
+size_t onssen_loss_phase_workspace_bytes(int B);
+int onssen_loss_phase_f32(const float* mask_a, const float* mask_b, int64_t m_sb, int64_t m_se, const float* mag_mix,
+                          const float* mag_s1, const float* mag_s2, const float* phase_a, const float* phase_b,
+                          const float* phase_s1, const float* phase_s2, int B, int TF, float* out_mask, float* out_phase,
+                          int32_t* perm, void* ws, size_t ws_bytes, void* stream);
+int onssen_loss_phase_grad_f32(const float* mask_a, const float* mask_b, int64_t m_sb, int64_t m_se, const float* mag_mix,
+                               const float* mag_s1, const float* mag_s2, const float* phase_a, const float* phase_b,
+                               const float* phase_s1, const float* phase_s2, int B, int TF, const float* g_mask,
+                               const float* g_phase, const int32_t* perm, float* d_mask_a, float* d_mask_b, int64_t d_sb,
+                               int64_t d_se, float* d_phase_a, float* d_phase_b, void* stream);
 size_t onssen_loss_dc_workspace_bytes(int B);
 int onssen_loss_dc_f32(const float* emb, const float* one_hot, const float* mag, int B, int TF, int D, int C,
                        float* per_utt, float* total_mag, void* ws, size_t ws_bytes, void* stream);
@@ -621,6 +646,14 @@ int onssen_sisnr_pit_backward_f32(const float* const* est_host, const int64_t* e
 int onssen_mask_istft_f32(const float* stft_ri, const float* mask, int64_t m_sb, int64_t m_sc, int64_t m_st,
                           int64_t m_sf, int B, int C, int T, int n_fft, int hop, int length, float* out,
                           void* stream);
+/* The same with a phase estimate per speaker (phase_net's reconstruction): speaker c's spectrum at a bin is
+ *   mask_c * |X| * (p_c.re + i p_c.im),  |X| = hypotf(Re X, Im X) in float32,
+ * instead of X * mask_c; p_c (B, T, F, 2) contiguous at phase + c*p_sc (8-byte aligned, p_sc even: two views of one buffer, or
+ * two tensors whose distance is p_sc floats).  The imaginary parts at DC and Nyquist are dropped like those of X above.
+ * Uniform batches only; n_fft in {256, 512, 1024}. */
+int onssen_phase_istft_f32(const float* stft_ri, const float* mask, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf,
+                           const float* phase, int64_t p_sc, int B, int C, int T, int n_fft, int hop, int length, float* out,
+                           void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Ragged batches (round 4): the reference evaluates WHOLE utterances one at a time (onssen/utils/test.py:29-41 with the

@@ -104,6 +104,10 @@ SIGNATURES = {
     "onssen_loss_mask_workspace_bytes": (_sz, [_i]),
     "onssen_loss_mask_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "onssen_loss_mask_grad_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "onssen_loss_phase_workspace_bytes": (_sz, [_i]),
+    "onssen_loss_phase_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "onssen_loss_phase_grad_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                        _i64, _i64, _vp, _vp, _vp]),
     "onssen_loss_dc_workspace_bytes": (_sz, [_i]),
     "onssen_batch_sdr_workspace_bytes": (_sz, [_i]),
     "onssen_batch_sdr_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -112,6 +116,7 @@ SIGNATURES = {
     "onssen_dc_head_grad_images_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "onssen_dc_cluster_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _sz, _i, _vp]),
     "onssen_mask_istft_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "onssen_phase_istft_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     # deep-clustering separation without the embedding round trip (round 4)
     "onssen_dc_compact_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "onssen_dc_compact_layout": (_i, [_i, _i, _i, _i, _vp, _vp]),
@@ -351,6 +356,18 @@ class Lib:
         self.check(self.dll.onssen_loss_mask_f32(ma, mb, m_sb, m_se, mag, s1, s2, c1, c2, B, TF, out, perm, ws, ws_bytes, stream),
                    "onssen_loss_mask_f32")
 
+    def loss_phase_workspace_bytes(self, B):
+        return int(self.dll.onssen_loss_phase_workspace_bytes(B))
+
+    def loss_phase(self, ma, mb, m_sb, m_se, mag, s1, s2, pa, pb, q1, q2, B, TF, out_mask, out_phase, perm, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_loss_phase_f32(ma, mb, m_sb, m_se, mag, s1, s2, pa, pb, q1, q2, B, TF, out_mask, out_phase, perm,
+                                                  ws, ws_bytes, stream), "onssen_loss_phase_f32")
+
+    def loss_phase_grad(self, ma, mb, m_sb, m_se, mag, s1, s2, pa, pb, q1, q2, B, TF, g_mask, g_phase, perm, da, db, d_sb, d_se,
+                        dpa, dpb, stream):
+        self.check(self.dll.onssen_loss_phase_grad_f32(ma, mb, m_sb, m_se, mag, s1, s2, pa, pb, q1, q2, B, TF, g_mask, g_phase, perm,
+                                                       da, db, d_sb, d_se, dpa, dpb, stream), "onssen_loss_phase_grad_f32")
+
     def loss_mask_grad(self, ma, mb, m_sb, m_se, mag, s1, s2, c1, c2, B, TF, g, perm, da, db, d_sb, d_se, stream):
         self.check(self.dll.onssen_loss_mask_grad_f32(ma, mb, m_sb, m_se, mag, s1, s2, c1, c2, B, TF, g, perm, da, db, d_sb, d_se,
                                                       stream), "onssen_loss_mask_grad_f32")
@@ -589,6 +606,10 @@ class Lib:
             return
         self.check(self.dll.onssen_mask_istft_f32(stft_ri, mask, m_sb, m_sc, m_st, m_sf, B, Cn, T, n_fft, hop,
                                                   length, out, stream), "onssen_mask_istft_f32")
+
+    def phase_istft(self, stft_ri, mask, m_sb, m_sc, m_st, m_sf, phase, p_sc, B, Cn, T, n_fft, hop, length, out, stream):
+        self.check(self.dll.onssen_phase_istft_f32(stft_ri, mask, m_sb, m_sc, m_st, m_sf, phase, p_sc, B, Cn, T, n_fft, hop,
+                                                   length, out, stream), "onssen_phase_istft_f32")
 
     def phase_input(self, x_mag, mask, m_sb, m_sc, m_st, m_sf, x_phase, B, Cn, T, F, out, stream):
         self.check(self.dll.onssen_phase_input_f32(x_mag, mask, m_sb, m_sc, m_st, m_sf, x_phase, B, Cn, T, F, out,

@@ -287,13 +287,17 @@ __global__ __launch_bounds__(256) void stft_logmag_kernel(const float* __restric
 // PAIR: two speakers per workgroup through ONE complex inverse FFT per frame: with Z = S_a + i S_b (both Hermitian),
 // ifft(Z) = s_a + i s_b because s_a and s_b are real -- half the butterflies of two real transforms.  blockIdx.y then
 // counts speaker pairs (the last pair of an odd C repeats its only speaker and drops the copy).
+// PHASE (phase_net's reconstruction, onssen_phase_istft_f32): speaker c's operand at a bin is mask_c * |X| * (p_c.re, p_c.im) with
+// the network's unit phase vector p_c instead of X * mask_c; p_c (B,T,F,2) sits at phase + c * p_sc.  |X| = hypotf(Re X, Im X) in
+// float32, as the reference's np.abs of a complex64 spectrum; the phases ride in the same batch of loads as the masks.
 __device__ const float kIstftOne = 1.0f;
-template <int N, int FB, bool PAIR>
+template <int N, int FB, bool PAIR, bool PHASE>
 __global__ __launch_bounds__(256) void mask_istft_kernel(const float* __restrict__ stft_ri,
                                                          const float* __restrict__ mask, long m_sb, long m_sc,
                                                          long m_st, long m_sf, int C, int T, int hop, int length,
                                                          int FR, float* __restrict__ out,
-                                                         const int* __restrict__ frames, const int* __restrict__ lengths) {
+                                                         const int* __restrict__ frames, const int* __restrict__ lengths,
+                                                         const float* __restrict__ phase, long p_sc) {
   constexpr int NS = PAIR ? 2 : 1;
   __shared__ double buf_re[4][fft_buf_len<N>()], buf_im[4][fft_buf_len<N>()];
   __shared__ float fr[NS][FB][N];   // windowed time-domain frames of this chunk (the reference's istft keeps them in
@@ -317,6 +321,8 @@ __global__ __launch_bounds__(256) void mask_istft_kernel(const float* __restrict
   // before this round's transform.  A frame past the end reads frame T-1 and is zeroed by a select.
   float2 xv[FPL];
   float mav[FPL], mbv[FPL], xnyq, manyq, mbnyq;
+  [[maybe_unused]] float2 pav[FPL], pbv[FPL];          // PHASE: the two speakers' phase vectors of this lane's bins
+  [[maybe_unused]] float xnyq_im, panyq, pbnyq;        // PHASE: Im X[N/2] (for |X|) and the real parts of the Nyquist phases
   auto fetch = [&](int round) {
     const int t = tfirst + round * 4 + wave, tt = t < Tb ? t : Tb - 1;
     const float* xs = stft_ri + ((long)b * T + tt) * F * 2;
@@ -335,6 +341,18 @@ __global__ __launch_bounds__(256) void mask_istft_kernel(const float* __restrict
     }
     manyq = ms0[(long)(N / 2) * sf];
     mbnyq = PAIR ? ms1[(long)(N / 2) * sf] : 0.f;
+    if constexpr (PHASE) {
+      const float* pa = phase + (long)c0 * p_sc + ((long)b * T + tt) * F * 2;
+      const float* pb = phase + (long)c1 * p_sc + ((long)b * T + tt) * F * 2;
+#pragma unroll
+      for (int k = 0; k < FPL; ++k) {
+        pav[k] = *reinterpret_cast<const float2*>(pa + 2 * (lane + 64 * k));
+        if constexpr (PAIR) pbv[k] = *reinterpret_cast<const float2*>(pb + 2 * (lane + 64 * k));
+      }
+      xnyq_im = xs[N + 1];
+      panyq = pa[N];
+      if constexpr (PAIR) pbnyq = pb[N];
+    }
   };
   fetch(0);                                            // (requested before the lane constants are built: their table loads and these are one round trip)
   constexpr bool kLaneConst = (N / 4 == 64) && !FftPlan<N>::kOdd;
@@ -363,9 +381,19 @@ __global__ __launch_bounds__(256) void mask_istft_kernel(const float* __restrict
     for (int k = 0; k < FPL; ++k) {
       // S_a = X * m_a (and S_b = X * m_b); c2r transforms ignore the imaginary part of DC / Nyquist
       const bool dc = (k == 0 && lane == 0);
+      double ar, ai, br, bi;
+      if constexpr (PHASE) {         // S_c = m_c |X| p_c
+        const double mag = active ? (double)hypotf(xv[k].x, xv[k].y) : 0.0;
+        const double ma = mag * (double)mav[k], mb = PAIR ? mag * (double)mbv[k] : 0.0;
+        ar = ma * (double)pav[k].x;
+        ai = dc ? 0.0 : ma * (double)pav[k].y;
+        br = PAIR ? mb * (double)pbv[k].x : 0.0;
+        bi = (PAIR && !dc) ? mb * (double)pbv[k].y : 0.0;
+      } else {
       const double xr = active ? (double)xv[k].x : 0.0, xi = (active && !dc) ? (double)xv[k].y : 0.0;
       const double ma = (double)mav[k], mb = (double)mbv[k];
-      const double ar = xr * ma, ai = xi * ma, br = PAIR ? xr * mb : 0.0, bi = PAIR ? xi * mb : 0.0;
+      ar = xr * ma; ai = xi * ma; br = PAIR ? xr * mb : 0.0; bi = PAIR ? xi * mb : 0.0;
+      }
       re[jf[k]] = ar - bi;           // Z[f] = S_a[f] + i S_b[f]
       im[jf[k]] = ai + br;
       if (!dc) {                     // Hermitian mirrors: Z[N-f] = conj(S_a[f]) + i conj(S_b[f])
@@ -374,9 +402,15 @@ __global__ __launch_bounds__(256) void mask_istft_kernel(const float* __restrict
       }
     }
     if (lane == 0) {
+      if constexpr (PHASE) {
+        const double mag = active ? (double)hypotf(xnyq, xnyq_im) : 0.0;
+        re[jnyq] = mag * (double)manyq * (double)panyq;
+        im[jnyq] = PAIR ? mag * (double)mbnyq * (double)pbnyq : 0.0;
+      } else {
       const double xr = active ? (double)xnyq : 0.0;
       re[jnyq] = xr * (double)manyq;
       im[jnyq] = PAIR ? xr * (double)mbnyq : 0.0;
+      }
     }
     if (round + 1 < FB / 4) fetch(round + 1);          // lands under this round's transform
     if constexpr (kLaneConst) fft_wave<N>(re, im, lane, true, &lcs); else fft_wave<N>(re, im, lane, true);

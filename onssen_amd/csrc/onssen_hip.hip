@@ -3,7 +3,8 @@
 //
 // Kernel inventory (one translation unit, the parts are the .inc files next to this one):
 //   fft.inc             stft_logmag_kernel (K1+K2: fp64 radix-4 FFT in LDS, one wavefront per PAIR of frames, fused log10(|X|+eps)),
-//                       mask_istft_kernel (K10: mask-apply + fp64 inverse FFT, two speakers per transform, gather overlap-add)
+//                       mask_istft_kernel (K10: mask-apply + fp64 inverse FFT, two speakers per transform, gather overlap-add;
+//                       with its phase flag the operand is mask * |X| * the network's phase estimate: onssen_phase_istft_f32)
 //   gemm.inc            linear_x3q_kernel (K3/K7/K8/K9 on pre-split bf16 images: 256|128 x 320|256 tiles staged by LDS-DMA into a swizzled
 //                       layout, 8 waves, register epilogues), linear_x3p_kernel (round-1 form: 256x160 tiles; batched weight gradients;
 //                       bias | sigmoid | grouped L2-norm), linear_x3_kernel / linear_kernel (fp32-A forms, exact-fp32 MFMA),
@@ -18,6 +19,7 @@
 //   loss_sdr.inc        loss_dc_* (value and gradient) / loss_mask_* (chimera mask term: value, winning assignment, gradient),
 //                       sdr_* (batch SI-SDR with best permutation, fp64 sums)
 //   loss_sisnr.inc      sisnr_* (Conv-TasNet's SI-SNR permutation-invariant training loss: value, assignment, gradient; fp64 moments)
+//   loss_phase.inc      loss_phase_* (phase_net's training loss: mask term and cosine phase term in one pass, assignment, gradient)
 //   pack.inc            one-off weight re-layout (gate permutation, MFMA fragment order, BatchNorm fold); training glue: dropout,
 //                       row-wise L2 normalisation and train-mode BatchNorm with their backward passes
 #include <hip/hip_runtime.h>
@@ -129,6 +131,7 @@ static unsigned& xcd_spin_limit() {
 #include "tasnet_stitch.inc" // Conv-TasNet long-form separation: window gather, permutation alignment, cross-fade
 #include "tasnet_run.inc" // Conv-TasNet: the one launch sequence behind the eval, ragged, training and stream entries
 #include "loss_sisnr.inc" // Conv-TasNet training: the SI-SNR permutation-invariant loss and its gradient
+#include "loss_phase.inc" // phase_net training: mask term + phase term of loss_phase in one pass, and their gradient
 
 // Co-tenant probe (tools/cotenant_probe.py): `workgroups` workgroups of `threads` threads that do nothing but hold their
 // CU for `ticks` ticks of the 100 MHz wall clock -- a stand-in for RCCL's channel kernels next to the persistent recurrences.
@@ -1366,9 +1369,11 @@ int onssen_debug_fft_stamps(long long* host_out, int n) {      // profile builds
 
 static int mask_istft_impl(const float* stft_ri, const float* mask, int64_t m_sb, int64_t m_sc, int64_t m_st,
                            int64_t m_sf, int B, int C, int T, int n_fft, int hop, int length, float* out,
-                           void* stream, const int32_t* frames, const int32_t* lengths) {
+                           void* stream, const int32_t* frames, const int32_t* lengths, const float* phase = nullptr,
+                           int64_t p_sc = 0) {
   if (!stft_ri || !out || B <= 0 || C <= 0 || T <= 0 || hop <= 0 || length <= 0 || hop > n_fft) return ONSSEN_E_ARG;
   if (reinterpret_cast<uintptr_t>(stft_ri) & 7u) return ONSSEN_E_ALIGN;               // (re, im) pairs are read as one 8-byte word
+  if (phase && ((reinterpret_cast<uintptr_t>(phase) & 7u) || (p_sc & 1))) return ONSSEN_E_ALIGN;   // so are the phase vectors
   // a chunk of FR hops of output needs FR + ceil(n_fft/hop) - 1 frames (one more when the chunk
   // origin n_fft/2 is not hop-aligned); FB frames fit in LDS
   // speakers go through the inverse FFT in pairs (one complex transform for two real frames) when there are at least
@@ -1401,9 +1406,16 @@ static int mask_istft_impl(const float* stft_ri, const float* mask, int64_t m_sb
   ONSSEN_CLEAR_ERROR();
   const dim3 grid((unsigned)ceil_div(length, FR * hop), (unsigned)(pair ? ceil_div(C, 2) : C), (unsigned)B), block(256);
   hipStream_t st = (hipStream_t)stream;
+  // (phase: the phase-aware operand of onssen_phase_istft_f32 -- the same geometry, its own instantiation of every form)
 #define ONSSEN_ISTFT(N_, FB_, PAIR_)                                                                                    \
-  hipLaunchKernelGGL((mask_istft_kernel<N_, FB_, PAIR_>), grid, block, 0, st, stft_ri, mask, (long)m_sb, (long)m_sc, \
-                     (long)m_st, (long)m_sf, C, T, hop, length, FR, out, frames, lengths)
+  do {                                                                                                                  \
+    if (phase)                                                                                                          \
+      hipLaunchKernelGGL((mask_istft_kernel<N_, FB_, PAIR_, true>), grid, block, 0, st, stft_ri, mask, (long)m_sb,      \
+                         (long)m_sc, (long)m_st, (long)m_sf, C, T, hop, length, FR, out, frames, lengths, phase, (long)p_sc); \
+    else                                                                                                                \
+      hipLaunchKernelGGL((mask_istft_kernel<N_, FB_, PAIR_, false>), grid, block, 0, st, stft_ri, mask, (long)m_sb,     \
+                         (long)m_sc, (long)m_st, (long)m_sf, C, T, hop, length, FR, out, frames, lengths, phase, (long)p_sc); \
+  } while (0)
   if (n_fft == 256) {
     if (!pair) ONSSEN_ISTFT(256, 16, false);
     else if (FB == 8) ONSSEN_ISTFT(256, 8, true);
@@ -1429,6 +1441,14 @@ int onssen_mask_istft_ragged_f32(const float* stft_ri, const float* mask, int64_
                                  const int32_t* lengths, float* out, void* stream) {
   if (!frames || !lengths) return ONSSEN_E_ARG;
   return mask_istft_impl(stft_ri, mask, m_sb, m_sc, m_st, m_sf, B, C, T, n_fft, hop, length, out, stream, frames, lengths);
+}
+
+int onssen_phase_istft_f32(const float* stft_ri, const float* mask, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf,
+                           const float* phase, int64_t p_sc, int B, int C, int T, int n_fft, int hop, int length, float* out,
+                           void* stream) {
+  if (!phase) return ONSSEN_E_ARG;
+  return mask_istft_impl(stft_ri, mask, m_sb, m_sc, m_st, m_sf, B, C, T, n_fft, hop, length, out, stream, nullptr, nullptr, phase,
+                         p_sc);
 }
 
 }  // extern "C"

@@ -322,6 +322,36 @@ class tester_chimera(tester):
         return mask_istft(ri, masks, self.hop_size, sig_ref.shape[-1], frames=frames, lengths=lengths), sig_ref.float()
 
 
+class tester_phase(tester):
+    """The phase network on the evaluation loader: the item is the chimera one (``[feature_mix]``, ``[stft_r_mix, stft_i_mix,
+    sig_ref]``), the network's second input is rebuilt from its labels, and the estimate is the inverse transform of
+    mask * |X| * predicted phase (``features.phase_istft``).  One utterance or one uniform batch per forward: phase_net has no
+    ragged forward, so ``eval(batch=K)`` with K > 1 raises."""
+
+    def __init__(self, args, hop_size=64):
+        super().__init__(args)
+        self.hop_size = hop_size
+
+    def eval(self, window=8, batch=1, bucket=1):
+        if int(batch) > 1:
+            raise ValueError("tester_phase: phase_net has no ragged forward; evaluate with batch=1")
+        return super().eval(window, 1, 1)
+
+    def _one(self, input, label, ragged):
+        feature_mix, = input
+        ri, _ = _mix_ri(label)
+        output = self.model([feature_mix.float(), ri])
+        sig_est, sig_ref = self.get_est_sig(input, label, output)
+        return batch_SDR_torch(sig_est, sig_ref)
+
+    def get_est_sig(self, input, label, output):
+        from .features import phase_istft
+        _, mask_A, mask_B, phase_A, phase_B = output
+        ri, sig_ref = _mix_ri(label)
+        masks = torch.stack([mask_A, mask_B], -1)
+        return phase_istft(ri, masks, [phase_A, phase_B], self.hop_size, sig_ref.shape[-1]), sig_ref.float()
+
+
 class tester_tasnet(tester):
     """egs/wsj0-2mix/tasnet/evaluate.py:11-29: the loader yields ``[mix (1, S')]``, ``[sig_ref (1, C, S')]`` per utterance and
     ConvTasNet's outputs are the estimates, cut to the reference's length.  ``eval()`` returns the mean SI-SDR.  ``batch=1``

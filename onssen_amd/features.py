@@ -92,6 +92,37 @@ def mask_istft(stft_ri, masks, hop_size=64, length=None, frames=None, lengths=No
     return out
 
 
+def phase_istft(stft_ri, masks, phases, hop_size=64, length=None):
+    """stft_ri (B,T,F,2); masks (B,T,F,C) (any strides); phases: C tensors (B,T,F,2), or one (C,B,T,F,2) ->
+    (B, C, length) float32: istft(mask_c * |stft| * (phase_c.re + i phase_c.im)) per speaker -- phase_net's reconstruction from
+    its masks and unit phase vectors (mask_istft re-uses the mixture's phase instead).  Uniform batches only.
+
+    The phase maps are read where they are when they lie at one common distance from each other (two slices of one buffer,
+    as phase_net's forward returns them; any two fp32 tensors); otherwise they are stacked first."""
+    if not stft_ri.is_cuda:
+        raise RuntimeError("phase_istft: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
+    stft_ri = stft_ri.float().contiguous()
+    B, T, F, _ = stft_ri.shape
+    n_fft = 2 * (F - 1)
+    if length is None:
+        length = hop_size * (T - 1)
+    masks = masks.float()
+    C = masks.shape[3]
+    phases = [p.float().contiguous() for p in (phases.unbind(0) if torch.is_tensor(phases) else phases)]
+    if len(phases) != C or any(tuple(p.shape) != (B, T, F, 2) for p in phases):
+        raise ValueError(f"phase_istft: expected {C} phase maps of shape {(B, T, F, 2)}, got {[tuple(p.shape) for p in phases]}")
+    step = {phases[c + 1].data_ptr() - phases[c].data_ptr() for c in range(C - 1)}
+    if len(step) > 1 or any(d % 8 for d in step) or phases[0].data_ptr() % 8:
+        stacked = torch.stack(phases)                    # kept alive until the launch below is queued
+        phases = list(stacked.unbind(0))
+        step = {phases[1].data_ptr() - phases[0].data_ptr()}
+    out = torch.empty(B, C, length, device=stft_ri.device, dtype=torch.float32)
+    get_lib().phase_istft(stft_ri.data_ptr(), masks.data_ptr(), masks.stride(0), masks.stride(3), masks.stride(1), masks.stride(2),
+                          phases[0].data_ptr(), step.pop() // 4 if step else 0, B, C, T, n_fft, hop_size, length, out.data_ptr(),
+                          _stream())
+    return out
+
+
 def training_labels(stft_mix, stft_s1, stft_s2, feature_mix, db_threshold=40.0, with_cos=False):
     """Label-side features of a batch of chunks on the GPU: counterparts of get_one_hot,
     np.abs and get_cos_difference (onssen/data/feature_utils.py:77-95, wsj0_2mix.py:130-152).

@@ -6,6 +6,8 @@ On a GPU the loss_dc value comes from ``onssen_loss_dc_f32`` (one pass over the 
 autograd needs it, the gradient from ``onssen_loss_dc_grad_f32`` (``dV = Z M`` from the same Gram: one more pass); on the CPU
 (tests, the gloo path) PyTorch ops with the same single-Gram forward and analytic backward.  ``ONSSEN_LOSS_HIP=0`` keeps the
 PyTorch form on the GPU.
+The phase network's loss (``loss_phase``): the same deep-clustering term, and the mask term and cosine phase term from
+``onssen_loss_phase_f32`` / ``onssen_loss_phase_grad_f32`` (one pass over the eleven maps forward, one elementwise pass backward).
 Semantics follow onssen/loss/loss_dc.py:6-44 and loss_util.py:4-11 exactly,
 including their quirks: the affinity terms are Frobenius *norms* (not squared
 norms) and the final product ``(B,) * (B,1)`` broadcasts to a (B, B) tensor
@@ -254,6 +256,118 @@ def loss_chimera_psa(output, label):
         t2 = torch.min(mag_mix, torch.relu(mag_s2 * cos_s2))
         lm = _mask_term(mask_A, mask_B, mag_mix, t1, t2)
     return le * 0.975 + lm * 0.025
+
+
+# ----------------------------------------------------------------------------- phase network loss
+last_phase_path = None
+
+
+def _phase_terms(mask_A, mask_B, phase_A, phase_B, mag_mix, mag_s1, mag_s2, phase_s1, phase_s2):
+    """(mask term, phase term), (B,) each, on PyTorch ops: the straight assignment where l1 < l2 strictly, else the swapped one."""
+    import torch.nn.functional as F
+    l1 = _l1(mask_A * mag_mix - mag_s1) + _l1(mask_B * mag_mix - mag_s2)
+    l2 = _l1(mask_B * mag_mix - mag_s1) + _l1(mask_A * mag_mix - mag_s2)
+    cos = lambda p, q: (mag_mix * F.cosine_similarity(p, q, dim=-1)).flatten(1).sum(dim=1)
+    p1 = -cos(phase_A, phase_s1) - cos(phase_B, phase_s2)
+    p2 = -cos(phase_B, phase_s1) - cos(phase_A, phase_s2)
+    straight = l1 < l2
+    return torch.where(straight, l1, l2), torch.where(straight, p1, p2)
+
+
+def _phase_interleaved_masks(mask_A, mask_B):
+    """The contiguous (..., 2) fp32 buffer whose two planes the masks are (the network's own when both are views of one,
+    as _mask_term_hip_autograd; anything else is interleaved by torch.stack)."""
+    base = getattr(mask_A, "_base", None)
+    dense, acc = [], 2
+    for n_i in reversed(mask_A.shape):
+        dense.insert(0, acc)
+        acc *= n_i
+    if (base is not None and getattr(mask_B, "_base", None) is base and base.dtype == torch.float32 and base.is_contiguous()
+            and base.numel() == 2 * mask_A.numel() and mask_A.stride() == mask_B.stride() == tuple(dense)
+            and mask_A.storage_offset() == base.storage_offset() and mask_B.storage_offset() == base.storage_offset() + 1):
+        return base
+    return torch.stack([mask_A.float(), mask_B.float()], -1)
+
+
+def _phase_terms_launch(masks, pa, pb, mag, s1, s2, q1, q2):
+    from .hip import get_lib
+    lib = get_lib()
+    B = mag.shape[0]
+    TF = mag[0].numel()
+    dev = mag.device
+    out_mask = torch.empty(B, device=dev, dtype=torch.float32)
+    out_phase = torch.empty(B, device=dev, dtype=torch.float32)
+    perm = torch.empty(B, device=dev, dtype=torch.int32)
+    ws = torch.empty(lib.loss_phase_workspace_bytes(B), dtype=torch.uint8, device=dev)
+    p = masks.data_ptr()
+    lib.loss_phase(p, p + 4, 2 * TF, 2, mag.data_ptr(), s1.data_ptr(), s2.data_ptr(), pa.data_ptr(), pb.data_ptr(), q1.data_ptr(),
+                   q2.data_ptr(), B, TF, out_mask.data_ptr(), out_phase.data_ptr(), perm.data_ptr(), ws.data_ptr(), ws.numel(),
+                   torch.cuda.current_stream().cuda_stream)
+    return out_mask, out_phase, perm
+
+
+class _PhaseTermsHip(torch.autograd.Function):
+    """(mask term, phase term) of loss_phase with their gradients on the device: ``onssen_loss_phase_f32`` reads the eleven maps
+    once and picks the assignment, ``onssen_loss_phase_grad_f32`` writes d/d(masks, phase_A, phase_B) in one pass.  ``masks`` is
+    the interleaved (B, ..., 2) buffer (see _MaskTermHip); the labels carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, masks, pa, pb, mag, s1, s2, q1, q2):
+        out_mask, out_phase, perm = _phase_terms_launch(masks, pa, pb, mag, s1, s2, q1, q2)
+        ctx.save_for_backward(masks, pa, pb, mag, s1, s2, q1, q2, perm)
+        return out_mask, out_phase
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_mask, g_phase):
+        from .hip import get_lib
+        masks, pa, pb, mag, s1, s2, q1, q2, perm = ctx.saved_tensors
+        B = mag.shape[0]
+        TF = mag[0].numel()
+        d, dpa, dpb = torch.empty_like(masks), torch.empty_like(pa), torch.empty_like(pb)
+        g_mask, g_phase = g_mask.float().contiguous(), g_phase.float().contiguous()
+        p, q = masks.data_ptr(), d.data_ptr()
+        get_lib().loss_phase_grad(p, p + 4, 2 * TF, 2, mag.data_ptr(), s1.data_ptr(), s2.data_ptr(), pa.data_ptr(), pb.data_ptr(),
+                                  q1.data_ptr(), q2.data_ptr(), B, TF, g_mask.data_ptr(), g_phase.data_ptr(), perm.data_ptr(),
+                                  q, q + 4, 2 * TF, 2, dpa.data_ptr(), dpb.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        return d, dpa, dpb, None, None, None, None, None
+
+
+def _phase_terms_hip(mask_A, mask_B, phase_A, phase_B, mag_mix, mag_s1, mag_s2, phase_s1, phase_s2, needs_grad):
+    lab = lambda t: t.detach().float().contiguous()
+    labels = [lab(t) for t in (mag_mix, mag_s1, mag_s2, phase_s1, phase_s2)]
+    masks = _phase_interleaved_masks(mask_A, mask_B)
+    pa, pb = phase_A.float().contiguous(), phase_B.float().contiguous()
+    if needs_grad:
+        return _PhaseTermsHip.apply(masks, pa, pb, *labels)
+    return _phase_terms_launch(masks.detach(), pa.detach(), pb.detach(), *labels)[:2]
+
+
+def loss_phase(output, label):
+    """onssen/loss/loss_phase.py:6-37 with its two defects repaired (it asserts six outputs and unpacks five, and hands loss_dc
+    its arguments in the wrong groups): 0.975 * loss_dc + 0.025 * mask term + 0.025 * phase term, (B,B) like the chimera losses.
+    The mask term is the L1 mask-inference term of the assignment with l1 < l2 strictly (a tie takes the swapped one, as
+    upstream's index does); the phase term is -sum |x| (cos(phase_A, t_A) + cos(phase_B, t_B)) under the same assignment, cos =
+    F.cosine_similarity over the (re, im) axis (each norm clamped at 1e-8; ``phase_s*`` are raw STFT values, 0 in silent bins).
+
+    On ROCm tensors with option ``loss`` = "1" both terms come from the loss_phase kernels (csrc/loss_phase.inc), with their
+    gradient when autograd needs it; on CPU tensors or with ``loss`` = "torch" from PyTorch ops.  ``last_phase_path`` ("hip" |
+    "aten") says which route the last call took.  The labels get no gradient."""
+    global last_phase_path
+    assert len(output) == 5, "There must be 5 tensors in the output"
+    assert len(label) == 6, "There must be 6 tensors in the label"
+    embedding, mask_A, mask_B, phase_A, phase_B = output
+    one_hot, mag_mix, mag_s1, mag_s2, phase_s1, phase_s2 = label
+    le = loss_dc([embedding], [one_hot, mag_mix])
+    if mask_A.is_cuda and options.get("loss") == "1":
+        last_phase_path = "hip"
+        lm, lp = _phase_terms_hip(mask_A, mask_B, phase_A, phase_B, mag_mix, mag_s1, mag_s2, phase_s1, phase_s2,
+                                  not _no_grad_needed(mask_A, mask_B, phase_A, phase_B))
+    else:
+        last_phase_path = "aten"
+        lm, lp = _phase_terms(mask_A, mask_B, phase_A, phase_B, mag_mix.detach(), mag_s1.detach(), mag_s2.detach(),
+                              phase_s1.detach(), phase_s2.detach())
+    return le * 0.975 + lm * 0.025 + lp * 0.025
 
 
 # ---- time-domain losses of Conv-TasNet (onssen/loss/loss_e2e.py:7-87) ------------------------------------------------------

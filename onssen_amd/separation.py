@@ -33,6 +33,22 @@ def separate_chimera(model, wav, window_size=256, hop_size=64, lengths=None):
     return out
 
 
+@recovering
+@torch.no_grad()
+def separate_phase(model, wav, window_size=256, hop_size=64):
+    """wav (B, n) cuda float32 -> (B, 2, n): phase_net's masks AND its phase estimates go into the inverse transform
+    (features.phase_istft); the mixture's phase is only the network's input.  Uniform batches (phase_net has no ragged forward)."""
+    from .features import phase_istft
+    logmag, ri = stft_logmag(wav, window_size, hop_size)
+    _, mask_A, mask_B, phase_A, phase_B = model([logmag, ri])
+    base = getattr(mask_A, "_base", None)            # the network's (B,T,F,2) mask buffer, when both masks are its planes
+    if base is None or getattr(mask_B, "_base", None) is not base or base.shape != mask_A.shape + (2,):
+        base = torch.stack([mask_A, mask_B], -1)
+    out = phase_istft(ri, base, [phase_A, phase_B], hop_size, wav.shape[-1])
+    _XcdStatus.flush()            # an aborted recurrence is caught HERE (and the call re-run, see `recovering`), not by the next call
+    return out
+
+
 @torch.no_grad()
 def separate_tasnet(model, waves):
     """Time-domain separation of whole utterances: ``waves`` a list of 1-D waveforms of any lengths (one device) -> a list of
