@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ONSSEN_ABI_VERSION 14   /* 14 (additions, no signature changed): onssen_sisnr_pit_* (Conv-TasNet's SI-SNR permutation-invariant training loss and its gradient).  14 (additions, no signature changed): onssen_tasnet_stream_* (stateful streaming inference of causal Conv-TasNet models).  14 (additions, no signature changed): onssen_tasnet_forward_ragged_f32 and onssen_tasnet_ragged_workspace_bytes (Conv-TasNet over whole utterances of different lengths).  14 (additions, no signature changed): onssen_tasnet_train_forward_f32, onssen_tasnet_backward_f32 and their two size queries (Conv-TasNet training).  14 (additions, no signature changed): onssen_tasnet_* (the Conv-TasNet separation forward).  14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
+#define ONSSEN_ABI_VERSION 14   /* 14 (additions, no signature changed): onssen_dc_cluster_k_f32 and onssen_dc_cluster_k_workspace_bytes (the deep-clustering back end for 2 .. 4 speakers).  14 (additions, no signature changed): onssen_sisnr_pit_* (Conv-TasNet's SI-SNR permutation-invariant training loss and its gradient).  14 (additions, no signature changed): onssen_tasnet_stream_* (stateful streaming inference of causal Conv-TasNet models).  14 (additions, no signature changed): onssen_tasnet_forward_ragged_f32 and onssen_tasnet_ragged_workspace_bytes (Conv-TasNet over whole utterances of different lengths).  14 (additions, no signature changed): onssen_tasnet_train_forward_f32, onssen_tasnet_backward_f32 and their two size queries (Conv-TasNet training).  14 (additions, no signature changed): onssen_tasnet_* (the Conv-TasNet separation forward).  14: onssen_blstm_pipe2_forward_ragged_f32 (the pipelined pair launch over a stream of RAGGED batches of whole utterances: each half of the launch runs its own batch's time steps and row lengths).  13: onssen_blstm_pipe2_* (a two-layer stack software-pipelined over consecutive calls: layer 1 of batch n-1 and layer 0 of batch n in ONE persistent launch, each on half of the XCDs).  12: onssen_log_magnitude_f32, onssen_cos_difference_f32, onssen_one_hot_f32 (the reference's stand-alone feature helpers).  11: onssen_wav_info, onssen_wav_read_batch_f32 (host-side batch RIFF reader of the file loader), onssen_lstm_pack_wih_image_f32, onssen_clip_adam_f32, onssen_lstm_train_backward_img_f32, onssen_lstm_pack_train_f32.  10: onssen_linear_x3p_norms, onssen_l2norm_rows_grad_y_f32, onssen_linear_x3p_batched_split_alt, onssen_x3_image_both_colsum_f32, onssen_dc_head_grad_images_f32, onssen_lstm_wgrad_images_f32, onssen_linear_x3t, onssen_blstm_x_image; ug = 24 (640 < H <= 768) in the persistent split-bf16 recurrence.  9: ragged batches of whole utterances (onssen_*_ragged_f32), the compacted deep-clustering back end, `tol` of onssen_dc_cluster_*, onssen_lstm_train_forward_form_f32.  8: onssen_linear_x3p_resid, onssen_linear_x3p_pair, onssen_x3_image_both_f32.  7: onssen_xcd_spin_limit, onssen_debug_cotenant_spin, chimera mask-loss gradient, compacted clustering.  6: onssen_dropout_f32, onssen_loss_dc_grad_f32, onssen_linear_x3p_batched_split, db_rows of onssen_lstm_train_backward_f32, l2norm_rows and bn_rows kernels; backward recurrence exchanges tagged partial sums.  5: status word [282] (non-finite h), W_hh fragment images unit-major, fp64 SDR workspace */
 
 #define ONSSEN_OK 0
 #define ONSSEN_E_ARG (-1)         /* invalid argument / unsupported shape */
@@ -721,6 +721,31 @@ int onssen_linear_x3p_compact(const uint16_t* a_img, int M, int K, const uint16_
                               int bf16_only, void* stream);
 int onssen_dc_cluster_compact_f32(int B, int T, int F, int D, int iters, float tol, float* masks, void* ws, size_t ws_bytes,
                                   int flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N2, K speakers: the deep-clustering back end for K = 2 .. 4 clusters (`num_spk = sig_ref.shape[1]`,
+ * `KMeans(n_clusters=num_spk)` and num_spk masks at egs/wsj0-2mix/deep_clustering/evaluate.py:33-44).  Threshold as above;
+ * masks (B,T,F,K): channel k is 1 where the bin is active and belongs to cluster k, every channel 0 on silent bins and on the
+ * padding of a ragged batch (frames: NULL, or frames[b] <= T frames per utterance, as onssen_dc_cluster_ragged_f32).
+ * The arithmetic is fixed, so the cluster numbering is deterministic and two calls give the same bits:
+ *   initialisation  c_0 = the embedding of the loudest bin (first maximum); c_k, k = 1 .. K-1, = the active bin that
+ *                   minimises max_{j<k} e.c_j (farthest point on unit vectors; ties to the smallest bin index; c_0 when
+ *                   there is no candidate).  K = 2: the initialisation of onssen_dc_cluster_f32.
+ *   iteration       label = argmin_k |c_k|^2 - 2 e.c_k (ties to the smallest k); new centroid = mean of its bins (an empty
+ *                   cluster keeps its centroid); stops at the bitwise fixed point, by the tol rule of onssen_dc_cluster_f32,
+ *                   or after `iters` iterations
+ *   masks           labels under the final centroids; cluster k is the one grown from c_k
+ * One form only: one assignment launch and one update launch per iteration (2 K + 2 iters + 1 launches per call), no
+ * inter-workgroup waits, no atomics.  D <= 32; emb and masks 16-byte aligned, ws 256-byte aligned (ONSSEN_E_ALIGN).
+ * ONSSEN_E_ARG: K outside 2 .. 4, D outside 1 .. 32, B, T or F < 1, iters < 0, tol < 0, a NULL pointer, or ws_bytes below
+ * what the size query returns (which is 0 for an unsupported shape); nothing is launched or written then.
+ * Workspace, written by every call (no zeroing by the owner): int32 words [4 b + 0] = Lloyd iterations run for utterance b
+ * and [4 b + 1] = 1 when it stopped by the fixed point or the tol rule, 0 when `iters` ran out ([4 b + 2], [4 b + 3]: the
+ * loudest bin, reserved); the float part (feature maximum, centroids, partial sums) follows 256-byte aligned. */
+size_t onssen_dc_cluster_k_workspace_bytes(int B, int T, int F, int D, int K);
+int onssen_dc_cluster_k_f32(const float* emb, const float* feature, int B, int T, const int32_t* frames /* may be NULL */,
+                            int F, int D, int K, float db_threshold, int iters, float tol, float* masks, void* ws,
+                            size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * H1  host side of the data front end (round 5): a batch of RIFF/WAVE files -> float32 mono rows of one host buffer.

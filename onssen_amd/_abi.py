@@ -123,6 +123,9 @@ SIGNATURES = {
     "onssen_dc_index_f32": (_i, [_vp, _i, _i, _vp, _i, _i, _f, _vp, _sz, _vp]),
     "onssen_linear_x3p_compact": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _f, _vp, _i64, _i, _vp, _i, _i64, _i, _vp]),
     "onssen_dc_cluster_compact_f32": (_i, [_i, _i, _i, _i, _i, _f, _vp, _vp, _sz, _i, _vp]),
+    # deep-clustering back end for 2 .. 4 speakers
+    "onssen_dc_cluster_k_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "onssen_dc_cluster_k_f32": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _i, _f, _vp, _vp, _sz, _vp]),
     # ragged batches of whole utterances (round 4)
     "onssen_stft_logmag_ragged_f32": (_i, [_vp, _i, _i, _i64, _vp, _i, _i, _f, _vp, _vp, _vp]),
     "onssen_blstm_forward_ragged_f32": (_i, [_vp, _i64, _i64, _i, _i, _vp, _i, _i, _i, _i, _pp, _pp, _pp, _vp, _vp, _sz, _i, _vp]),
@@ -647,6 +650,10 @@ class Lib:
     def dc_cluster_compact(self, B, T, F, D, iters, masks, ws, ws_bytes, stream, flags=0, tol=1e-4):
         self.check(self.dll.onssen_dc_cluster_compact_f32(B, T, F, D, iters, tol, masks, ws, ws_bytes, flags, stream),
                    "onssen_dc_cluster_compact_f32")
+
+    def dc_cluster_k(self, emb, feat, B, T, F, D, K, db, iters, masks, ws, ws_bytes, stream, frames=None, tol=1e-4):
+        self.check(self.dll.onssen_dc_cluster_k_f32(emb, feat, B, T, frames, F, D, K, db, iters, tol, masks, ws, ws_bytes, stream),
+                   "onssen_dc_cluster_k_f32")
 
     def dc_cluster(self, emb, feat, B, T, F, D, db, iters, masks, ws, ws_bytes, stream, flags=0, frames=None, tol=1e-4):
         if frames is not None:       # ragged batch: utterance b owns frames[b] * F bins

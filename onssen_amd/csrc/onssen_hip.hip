@@ -16,6 +16,8 @@
 //   lstm_run.inc        host code: the BLSTM's geometry, workspace layouts, launchers and C ABI entries (forward, pipelined pair, training)
 //   labels_cluster.inc  labels_kernel (training labels), kmeans2_* (deep-clustering back end: compaction of the active bins, all
 //                       Lloyd iterations in one persistent launch with register-resident rows; launch-per-iteration fallback)
+//   kmeans_k.inc        kmeansk_* (the same back end for 2 .. 4 speakers: farthest-point initialisation, launch-per-iteration Lloyd,
+//                       K-channel masks)
 //   loss_sdr.inc        loss_dc_* (value and gradient) / loss_mask_* (chimera mask term: value, winning assignment, gradient),
 //                       sdr_* (batch SI-SDR with best permutation, fp64 sums)
 //   loss_sisnr.inc      sisnr_* (Conv-TasNet's SI-SNR permutation-invariant training loss: value, assignment, gradient; fp64 moments)
@@ -118,6 +120,7 @@ static unsigned& xcd_spin_limit() {
 #include "pack.inc"
 #include "gemm.inc"
 #include "labels_cluster.inc"
+#include "kmeans_k.inc"     // deep-clustering back end for 2 .. 4 speakers: its kernels and its C ABI entries
 #include "lstm.inc"
 #include "lstm_bwd.inc"
 #include "lstm_run.inc"    // BLSTM host side: geometry, workspace layouts, launchers and the C ABI entries over lstm.inc / lstm_bwd.inc

@@ -189,8 +189,9 @@ def _mix_ri(label):
 
 
 class tester_dc(tester):
-    """egs/wsj0-2mix/deep_clustering/evaluate.py:11-47: threshold at max - 40/20, 2-means on the active bins'
-    embeddings, binary masks, mask-apply + iSTFT -- on the device (``host_kmeans=True``: upstream's sklearn path)."""
+    """egs/wsj0-2mix/deep_clustering/evaluate.py:11-47: threshold at max - 40/20, K-means on the active bins'
+    embeddings (K = the number of sources in ``sig_ref``, 2 .. 4), binary masks, mask-apply + iSTFT -- on the device
+    (``host_kmeans=True``: upstream's sklearn path)."""
 
     def __init__(self, args, hop_size=64, host_kmeans=False):
         super().__init__(args)
@@ -201,8 +202,9 @@ class tester_dc(tester):
         batches (round 6c, ``separation.DCRaggedPipeline``: layer 1 of forward i-1 and layer 0 of forward i share one persistent
         launch; the active bins' embedding goes straight from the head GEMM into the clustering), same SI-SDR per utterance bit for
         bit -- 1.35 x the utterances per second of the plain ``batch`` = 16 loop.  ``pipeline=False``, ``host_kmeans``, other models,
-        modes or batch sizes: the plain loop.  An aborted persistent launch re-runs the forwards it touched on the plain loop's
-        recovery path."""
+        modes or batch sizes: the plain loop -- also for every single forward whose ``sig_ref`` holds other than two sources (the
+        pipeline is two-speaker; ``get_est_sig`` clusters into ``sig_ref.shape[1]`` speakers).  An aborted persistent launch re-runs
+        the forwards it touched on the plain loop's recovery path."""
         import warnings
         from .nn._core import XcdAborted, _XcdPolicy, _XcdStatus
         from .separation import DCRaggedPipeline
@@ -263,6 +265,12 @@ class tester_dc(tester):
                 ri, sig_ref = _mix_ri(label)
                 B, T, _ = feature_mix.shape
                 n = sig_ref.shape[-1]
+                if sig_ref.shape[1] != 2:         # the pipeline is two-speaker (DCRaggedPipeline): this forward takes the plain loop
+                    t, c = drain()
+                    total, count, pipe = total + t, count + c, None
+                    t, c = plain([item], False)
+                    total, count = total + t, count + c
+                    continue
                 if pipe is not None and (B != pipe.B or T > pipe.T_cap or n > pipe.n_cap):
                     t, c = drain()
                     total, count, pipe = total + t, count + c, None
@@ -291,19 +299,19 @@ class tester_dc(tester):
         feature_mix, = input
         embedding, = output
         ri, sig_ref = _mix_ri(label)
+        num_spk = int(sig_ref.shape[1])               # evaluate.py:33: the speaker count comes from the references
         if self.host_kmeans and frames is not None:
             raise ValueError("tester_dc(host_kmeans=True) evaluates one utterance per forward (eval(batch=1))")
         if self.host_kmeans:
-            import numpy as np
             from sklearn.cluster import KMeans
-            masks = torch.zeros(tuple(feature_mix.shape) + (2,), device=feature_mix.device)
+            from .separation import _host_label_masks
+            masks = torch.zeros(tuple(feature_mix.shape) + (num_spk,), device=feature_mix.device)
             for b in range(feature_mix.shape[0]):
                 act = feature_mix[b] >= (feature_mix[b].max() - 40 / 20)
-                lab = KMeans(n_clusters=2, random_state=0, n_init=10).fit_predict(embedding[b][act].cpu().numpy())
-                lab = torch.from_numpy(lab.astype(np.int64)).to(feature_mix.device).float()
-                masks[b][act] = torch.stack([lab, 1.0 - lab], -1)
+                lab = KMeans(n_clusters=num_spk, random_state=0, n_init=10).fit_predict(embedding[b][act].cpu().numpy())
+                masks[b][act] = _host_label_masks(lab, num_spk, feature_mix.device)
         else:
-            masks = dc_masks(embedding, feature_mix.float(), 40.0, frames=frames)
+            masks = dc_masks(embedding, feature_mix.float(), 40.0, frames=frames, num_speaker=num_spk)
         return mask_istft(ri, masks, self.hop_size, sig_ref.shape[-1], frames=frames, lengths=lengths), sig_ref.float()
 
 

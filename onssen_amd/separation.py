@@ -276,9 +276,14 @@ def dc_masks_from_features(model, logmag, db_threshold=40.0, iters=20, frames=No
     return masks
 
 
-def dc_masks(emb, logmag, db_threshold=40.0, iters=20, frames=None, tol=1e-4):
+def dc_masks(emb, logmag, db_threshold=40.0, iters=20, frames=None, tol=1e-4, num_speaker=2):
     """Binary deep-clustering masks (B,T,F,2) on the device: threshold at max - db/20, 2-means on the active
     bins' embeddings (counterpart of evaluate.py:36-41, where it is sklearn on the host).
+
+    ``num_speaker`` = 3 or 4: K-means for that many speakers (evaluate.py:33-44 takes the count from ``sig_ref``) and masks
+    (B,T,F,K), channel k = the cluster grown from the k-th centroid of a deterministic farthest-point initialisation
+    (``onssen_dc_cluster_k_f32``).  That route has the launch-per-iteration form only -- no persistent
+    launch, no waits, nothing to recover -- and takes ``frames`` like the two-speaker one.  Anything but 2, 3, 4: ValueError.
 
     Default: the active bins are compacted once and all Lloyd iterations run in ONE persistent launch (8 workgroups per
     utterance meeting at a counter); its waits are bounded, and a wait that gave up is reported like an aborted recurrence
@@ -294,9 +299,25 @@ def dc_masks(emb, logmag, db_threshold=40.0, iters=20, frames=None, tol=1e-4):
     from . import _abi
     from .hip import get_lib
     from .nn._core import _XcdPolicy, _XcdSerial, _XcdStatus
+    K = int(num_speaker)
+    if K not in (2, 3, 4):
+        raise ValueError(f"dc_masks: num_speaker must be 2, 3 or 4, got {num_speaker}")
     lib = get_lib()
     B, T, F, D = emb.shape
     emb, logmag = emb.contiguous(), logmag.contiguous()
+    if K > 2:
+        nb = int(lib.dll.onssen_dc_cluster_k_workspace_bytes(B, T, F, D, K))
+        if nb == 0:
+            raise ValueError(f"dc_masks: unsupported shape for num_speaker = {K}: embedding {tuple(emb.shape)} (embedding_dim <= 32)")
+        ws = _cluster_ws(emb.device, (emb.device, B, T, F, D, "k", K), nb, 0, frames is not None)      # (rewritten by every call)
+        masks = torch.empty(B, T, F, K, device=emb.device, dtype=torch.float32)
+        if frames is not None:
+            from .features import _lengths_i32
+            frames = _lengths_i32(frames, B, T, emb.device, "frames")
+        lib.dc_cluster_k(emb.data_ptr(), logmag.data_ptr(), B, T, F, D, K, float(db_threshold), iters, masks.data_ptr(),
+                         ws.data_ptr(), nb, torch.cuda.current_stream().cuda_stream,
+                         frames=frames.data_ptr() if frames is not None else None, tol=float(tol))
+        return masks
     nb = int(lib.dll.onssen_dc_cluster_workspace_bytes(B, T, F, D))
     head = lib.dc_compact_layout(B, T, F, D)[1]        # the library's own offset of the compacted array = the header's size
     ws = _cluster_ws(emb.device, (emb.device, B, T, F, D), nb, head, frames is not None)
@@ -317,25 +338,40 @@ def dc_masks(emb, logmag, db_threshold=40.0, iters=20, frames=None, tol=1e-4):
     return masks
 
 
+def _host_label_masks(label, K, device):
+    """sklearn labels of the active bins -> their mask rows (n, K): (label, 1 - label) for two speakers, as ever; one-hot
+    (``mask[i, embedding_labels == i] = 1``, evaluate.py:39-41) for more."""
+    lab = torch.from_numpy(label.astype(np.int64)).to(device)
+    if K == 2:
+        return torch.stack([lab.float(), 1.0 - lab.float()], -1)
+    return torch.nn.functional.one_hot(lab, K).float()
+
+
 @recovering
 @torch.no_grad()
-def separate_dc(model, wav, window_size=256, hop_size=64, db_threshold=40.0, host_kmeans=False, lengths=None):
+def separate_dc(model, wav, window_size=256, hop_size=64, db_threshold=40.0, host_kmeans=False, lengths=None, num_speaker=2):
     """Deep-clustering separation, waveform in -> (B, 2, n) waveforms out, entirely on the GPU
     (STFT -> network -> threshold + 2-means -> binary masks -> mask-apply + iSTFT).  ``host_kmeans=True``
-    clusters with sklearn KMeans(n_clusters=2, random_state=0) on the host exactly as upstream does
+    clusters with sklearn KMeans(n_clusters=num_speaker, random_state=0) on the host exactly as upstream does
     (egs/wsj0-2mix/deep_clustering/evaluate.py:36-38); the two differ only in the arbitrary cluster
     numbering and in bins that sit between the clusters.
+
+    ``num_speaker`` = 3 or 4 -> (B, num_speaker, n): the same network, K-means for that many speakers on its embedding
+    (``dc_masks(num_speaker=)``; the route that skips the embedding is two-speaker, so the embedding is materialised).
 
     ``lengths`` (B,): a RAGGED batch of whole utterances -- row b holds lengths[b] valid samples of the n it is padded to
     (the reference separates them one at a time, onssen/utils/test.py:29-41; together they fill the chip).  Every row's
     result inside its own length is bit for bit what the batch-1 call on wav[b:b+1, :lengths[b]] returns; zeros after it."""
+    K = int(num_speaker)
+    if K not in (2, 3, 4):
+        raise ValueError(f"separate_dc: num_speaker must be 2, 3 or 4, got {num_speaker}")
     lengths, frames = _ragged(wav, lengths, hop_size)
     logmag, ri = stft_logmag(wav, window_size, hop_size, lengths=lengths)
     if not host_kmeans:
-        masks = dc_masks_from_features(model, logmag, db_threshold, frames=frames)      # the embedding never leaves the GEMM ...
+        masks = dc_masks_from_features(model, logmag, db_threshold, frames=frames) if K == 2 else None   # the embedding never leaves the GEMM ...
         if masks is None:                                                                 # ... unless this forward cannot do that
             emb, = model([logmag]) if frames is None else model([logmag], frames=frames)
-            masks = dc_masks(emb, logmag, db_threshold, frames=frames)
+            masks = dc_masks(emb, logmag, db_threshold, frames=frames, num_speaker=K)
         out = mask_istft(ri, masks, hop_size, wav.shape[-1], frames=frames, lengths=lengths)
         _XcdStatus.flush()        # an aborted recurrence is reported by THIS call, not by the next one
         return out
@@ -345,13 +381,12 @@ def separate_dc(model, wav, window_size=256, hop_size=64, db_threshold=40.0, hos
     _XcdStatus.flush()
     from sklearn.cluster import KMeans
     B, T, F, D = emb.shape
-    masks = torch.zeros(B, T, F, 2, device=wav.device, dtype=torch.float32)
+    masks = torch.zeros(B, T, F, K, device=wav.device, dtype=torch.float32)
     for b in range(B):   # upstream evaluates with batch 1 (evaluate.py:34-35)
         feat = logmag[b]
         act = feat >= (feat.max() - db_threshold / 20.0)
-        label = KMeans(n_clusters=2, random_state=0, n_init=10).fit_predict(emb[b][act].cpu().numpy())
-        lab = torch.from_numpy(label.astype(np.int64)).to(wav.device).float()
-        masks[b][act] = torch.stack([lab, 1.0 - lab], -1)
+        label = KMeans(n_clusters=K, random_state=0, n_init=10).fit_predict(emb[b][act].cpu().numpy())
+        masks[b][act] = _host_label_masks(label, K, wav.device)
     return mask_istft(ri, masks, hop_size, wav.shape[-1])
 
 
@@ -373,7 +408,8 @@ class DCPipeline:
 
     Needs an eval-mode ``deep_clustering`` with num_layers = 2, hidden <= 640, B <= 32 in the default split-bf16 arithmetic on the
     persistent recurrence; anything else raises (use ``separate_dc``).  A launch that gave up a bounded wait is reported by the
-    next ``push`` / ``flush`` (XcdAborted; ``separate_dc_stream`` re-runs the affected batches with ``separate_dc``)."""
+    next ``push`` / ``flush`` (XcdAborted; ``separate_dc_stream`` re-runs the affected batches with ``separate_dc``).
+    Two speakers only (the compacted clustering it ends in is the 2-means): ``separate_dc(num_speaker=)`` separates three or four."""
 
     def __init__(self, model, B, n_samples, window_size=256, hop_size=64, db_threshold=40.0, iters=20, tol=1e-4, graph=True):
         from . import _abi
@@ -556,7 +592,8 @@ class DCRaggedPipeline:
     Every utterance's result inside its own length is bit for bit what ``separate_dc(model, wav, lengths=lengths)`` gives it (stacked
     tiles in both: a tile column never sees its neighbours), i.e. what the batch-1 call on that utterance returns; zeros after it.
     Eager launches (a new longest utterance per batch: nothing to capture); buffers are sized once for ``n_cap`` samples per row.
-    Needs what ``DCPipeline`` needs, with B <= 16."""
+    Needs what ``DCPipeline`` needs, with B <= 16; two speakers only, like it (``tester_dc.eval`` sends a forward whose references
+    hold another number of sources through its plain loop)."""
 
     @staticmethod
     def why_not(model, B, window_size=256):
