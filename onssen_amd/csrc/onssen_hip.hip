@@ -121,6 +121,7 @@ static unsigned& xcd_spin_limit() {
 #include "gemm.inc"
 #include "labels_cluster.inc"
 #include "kmeans_k.inc"     // deep-clustering back end for 2 .. 4 speakers: its kernels and its C ABI entries
+#include "dc_run.inc"       // deep-clustering 2-means host side: one workspace layout, one Lloyd launcher, the C ABI entries over labels_cluster.inc
 #include "lstm.inc"
 #include "lstm_bwd.inc"
 #include "lstm_run.inc"    // BLSTM host side: geometry, workspace layouts, launchers and the C ABI entries over lstm.inc / lstm_bwd.inc
@@ -1206,162 +1207,6 @@ int onssen_one_hot_f32(const float* feature_mix, const float* mag_s1, const floa
                      total, db_threshold, one_hot);
   ONSSEN_LAUNCH_CHECK();
   return ONSSEN_OK;
-}
-
-// workspace: [B][stride] float header (feature max, centroids, partial sums, done flag) | [B][km::IW] ints + status word |
-// compacted active rows [B][T*F][D] (persistent form)
-static size_t dc_cluster_header_floats(int B, int D) { return (size_t)B * (1 + 2 * D + km::NBLK * 2 * (D + 1) + 1); }
-size_t onssen_dc_cluster_status_offset(int B, int D) {
-  if (B <= 0 || D <= 0 || D > km::DMAX) return 0;
-  return align256(dc_cluster_header_floats(B, D) * sizeof(float)) + (size_t)B * km::IW * sizeof(int);
-}
-size_t onssen_dc_cluster_workspace_bytes(int B, int T, int F, int D) {
-  if (B <= 0 || T <= 0 || F <= 0 || D <= 0 || D > km::DMAX) return 0;
-  return align256(onssen_dc_cluster_status_offset(B, D) + 256) + (size_t)B * T * F * D * sizeof(float);
-}
-
-static int dc_cluster_impl(const float* emb, const float* feature, int B, int T, int F, int D, float db_threshold,
-                           int iters, float tol, float* masks, void* ws, size_t ws_bytes, int flags, void* stream, const int32_t* frames) {
-  if (!emb || !feature || !masks || !ws || B <= 0 || T <= 0 || F <= 0 || D <= 0 || D > km::DMAX || iters < 0 || !(tol >= 0.f))
-    return ONSSEN_E_ARG;
-  if (ws_bytes < onssen_dc_cluster_workspace_bytes(B, T, F, D)) return ONSSEN_E_WORKSPACE;
-  if (!aligned16(emb) || (reinterpret_cast<uintptr_t>(ws) & 255u)) return ONSSEN_E_ALIGN;
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  const long per_utt = (long)T * F, stride = 1 + 2 * D + km::NBLK * 2 * (D + 1) + 1;
-  float* w = (float*)ws;
-  int* iw = (int*)((char*)ws + align256(dc_cluster_header_floats(B, D) * sizeof(float)));
-  unsigned* status = (unsigned*)((char*)ws + onssen_dc_cluster_status_offset(B, D));
-  float* comp = (float*)((char*)ws + align256(onssen_dc_cluster_status_offset(B, D) + 256));
-  const bool persistent = !(flags & ONSSEN_DC_CLUSTER_LAUNCH_PER_ITERATION);
-  const dim3 sgrid(km::NBLK, (unsigned)B);
-  hipLaunchKernelGGL((kmeans2_search_kernel<0>), sgrid, dim3(256), 0, st, emb, feature, per_utt, D, db_threshold, w, stride, frames, F);
-  hipLaunchKernelGGL((kmeans2_pick_kernel<0>), dim3((unsigned)B), dim3(64), 0, st, emb, per_utt, D, w, stride, iw);
-#define ONSSEN_KM_ASSIGN(MODE_, OUT_)                                                                                      \
-  do {                                                                                                                   \
-    if (D == 20) hipLaunchKernelGGL((kmeans2_assign_kernel<MODE_, 20>), dim3(km::NBLK, (unsigned)B), dim3(256), 0, st, emb, \
-                                    feature, per_utt, D, db_threshold, w, stride, OUT_, frames, F);                         \
-    else hipLaunchKernelGGL((kmeans2_assign_kernel<MODE_, 0>), dim3(km::NBLK, (unsigned)B), dim3(256), 0, st, emb, feature,  \
-                            per_utt, D, db_threshold, w, stride, OUT_, frames, F);                                           \
-  } while (0)
-  if (persistent) {
-    // active bins compacted once (the same pass finds the second centroid), then ALL Lloyd iterations in one launch per <= 32
-    // utterances (km::NBP workgroups of km::LT threads each, one per CU: 256 workgroups fill the chip exactly)
-    hipLaunchKernelGGL((kmeans2_count_kernel<false>), sgrid, dim3(256), 0, st, feature, per_utt, db_threshold, w, stride, iw, frames, F, D);
-    if (D == 20) hipLaunchKernelGGL((kmeans2_compact_kernel<20>), sgrid, dim3(256), 0, st, emb, feature, per_utt, D, db_threshold, w, stride, iw, comp, frames, F);
-    else hipLaunchKernelGGL((kmeans2_compact_kernel<0>), sgrid, dim3(256), 0, st, emb, feature, per_utt, D, db_threshold, w, stride, iw, comp, frames, F);
-    hipLaunchKernelGGL((kmeans2_pick_kernel<1>), dim3((unsigned)B), dim3(64), 0, st, emb, per_utt, D, w, stride, (int*)nullptr);
-    // (a wait that gives up leaves status = 1: the host sees it and runs the launch-per-iteration form)
-    const unsigned spin = xcd_spin_limit();
-    // one workgroup per CU: as many utterances per launch as the device has CUs / NBP (32 on a whole MI355X; fewer in a
-    // partitioned mode -- a launch that cannot be co-resident would only be caught by its bounded waits)
-    static const int lloyd_utts = [] {
-      int dev = 0, cus = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-      const int n = cus / km::NBP;
-      return n < 1 ? 1 : n > 32 ? 32 : n;
-    }();
-    for (int u0 = 0; u0 < B && iters > 0; u0 += lloyd_utts) {
-      const int nutt = B - u0 < lloyd_utts ? B - u0 : lloyd_utts;
-      const dim3 lgrid((unsigned)(ceil_div(nutt, 8) * 8 * km::NBP));
-      if (D == 20) hipLaunchKernelGGL((kmeans2_lloyd_kernel<20>), lgrid, dim3(km::LT), 0, st, (const float*)comp, per_utt, D, iters, w, stride, iw, u0, nutt, spin, status, tol);
-      else hipLaunchKernelGGL((kmeans2_lloyd_kernel<0>), lgrid, dim3(km::LT), 0, st, (const float*)comp, per_utt, D, iters, w, stride, iw, u0, nutt, spin, status, tol);
-    }
-  } else {
-    hipLaunchKernelGGL((kmeans2_search_kernel<1>), sgrid, dim3(256), 0, st, emb, feature, per_utt, D, db_threshold, w, stride, frames, F);
-    hipLaunchKernelGGL((kmeans2_pick_kernel<1>), dim3((unsigned)B), dim3(64), 0, st, emb, per_utt, D, w, stride, (int*)nullptr);
-    for (int it = 0; it < iters; ++it) {
-      ONSSEN_KM_ASSIGN(0, (float*)nullptr);
-      hipLaunchKernelGGL(kmeans2_update_kernel, dim3((unsigned)B), dim3(256), 0, st, D, km::NBLK, w, stride, tol);
-    }
-  }
-  ONSSEN_KM_ASSIGN(1, masks);
-#undef ONSSEN_KM_ASSIGN
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-// ---- compacted form (round 4): index -> (the fc_dc GEMM scatters the active rows) -> cluster ---------------------------------
-size_t onssen_dc_compact_workspace_bytes(int B, int T, int F, int D) {
-  const size_t base = onssen_dc_cluster_workspace_bytes(B, T, F, D);
-  return base ? align256(base) + align256((size_t)B * T * F * sizeof(int32_t) + 16) : 0;   // (+16: onssen_linear_x3p_compact reads the map in 16-byte words)
-}
-
-int onssen_dc_compact_layout(int B, int T, int F, int D, size_t* comp_offset, size_t* dest_offset) {
-  if (onssen_dc_cluster_workspace_bytes(B, T, F, D) == 0) return ONSSEN_E_ARG;
-  if (comp_offset) *comp_offset = align256(onssen_dc_cluster_status_offset(B, D) + 256);
-  if (dest_offset) *dest_offset = align256(onssen_dc_cluster_workspace_bytes(B, T, F, D));
-  return ONSSEN_OK;
-}
-
-int onssen_dc_index_f32(const float* feature, int B, int T, const int32_t* frames, int F, int D, float db_threshold, void* ws,
-                        size_t ws_bytes, void* stream) {
-  if (!feature || !ws || B <= 0 || T <= 0 || F <= 0 || D <= 0 || D > km::DMAX) return ONSSEN_E_ARG;
-  if (ws_bytes < onssen_dc_compact_workspace_bytes(B, T, F, D)) return ONSSEN_E_WORKSPACE;
-  if (reinterpret_cast<uintptr_t>(ws) & 255u) return ONSSEN_E_ALIGN;
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  const long per_utt = (long)T * F, stride = 1 + 2 * D + km::NBLK * 2 * (D + 1) + 1;
-  float* w = (float*)ws;
-  int* iw = (int*)((char*)ws + align256(dc_cluster_header_floats(B, D) * sizeof(float)));
-  size_t dest_off = 0;
-  onssen_dc_compact_layout(B, T, F, D, nullptr, &dest_off);
-  int* dest = (int*)((char*)ws + dest_off);
-  const dim3 sgrid(km::NBLK, (unsigned)B);
-  hipLaunchKernelGGL((kmeans2_search_kernel<0>), sgrid, dim3(256), 0, st, (const float*)nullptr, feature, per_utt, D, db_threshold, w, stride, frames, F);
-  hipLaunchKernelGGL((kmeans2_count_kernel<true>), sgrid, dim3(256), 0, st, feature, per_utt, db_threshold, w, stride, iw, frames, F, D);
-  hipLaunchKernelGGL(kmeans2_index_kernel, sgrid, dim3(256), 0, st, feature, per_utt, db_threshold, (const float*)w, stride, iw, dest, frames, F, D);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-int onssen_dc_cluster_compact_f32(int B, int T, int F, int D, int iters, float tol, float* masks, void* ws, size_t ws_bytes,
-                                  int flags, void* stream) {
-  if (!masks || !ws || B <= 0 || T <= 0 || F <= 0 || D <= 0 || D > km::DMAX || iters < 0 || !(tol >= 0.f)) return ONSSEN_E_ARG;
-  if (flags & ONSSEN_DC_CLUSTER_LAUNCH_PER_ITERATION) return ONSSEN_E_ARG;      // the compacted form IS the persistent form
-  if (ws_bytes < onssen_dc_compact_workspace_bytes(B, T, F, D)) return ONSSEN_E_WORKSPACE;
-  if (reinterpret_cast<uintptr_t>(ws) & 255u) return ONSSEN_E_ALIGN;
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  const long per_utt = (long)T * F, stride = 1 + 2 * D + km::NBLK * 2 * (D + 1) + 1;
-  float* w = (float*)ws;
-  int* iw = (int*)((char*)ws + align256(dc_cluster_header_floats(B, D) * sizeof(float)));
-  unsigned* status = (unsigned*)((char*)ws + onssen_dc_cluster_status_offset(B, D));
-  size_t comp_off = 0, dest_off = 0;
-  onssen_dc_compact_layout(B, T, F, D, &comp_off, &dest_off);
-  const float* comp = (const float*)((char*)ws + comp_off);
-  const int* dest = (const int*)((char*)ws + dest_off);
-  const dim3 sgrid(km::NBLK, (unsigned)B);
-  // (the farthest-point initialisation rides in the Lloyd launch's first pass: INIT)
-  const unsigned spin = xcd_spin_limit();
-  static const int lloyd_utts = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    const int n = cus / km::NBP;
-    return n < 1 ? 1 : n > 32 ? 32 : n;
-  }();
-  for (int u0 = 0; u0 < B; u0 += lloyd_utts) {     // (also with iters = 0: pass 0 initialises the centroids)
-    const int nutt = B - u0 < lloyd_utts ? B - u0 : lloyd_utts;
-    const dim3 lgrid((unsigned)(ceil_div(nutt, 8) * 8 * km::NBP));
-    if (D == 20) hipLaunchKernelGGL((kmeans2_lloyd_kernel<20, true>), lgrid, dim3(km::LT), 0, st, comp, per_utt, D, iters, w, stride, iw, u0, nutt, spin, status, tol, dest);
-    else hipLaunchKernelGGL((kmeans2_lloyd_kernel<0, true>), lgrid, dim3(km::LT), 0, st, comp, per_utt, D, iters, w, stride, iw, u0, nutt, spin, status, tol, dest);
-  }
-  if (D == 20) hipLaunchKernelGGL((kmeans2_mask_compact_kernel<20>), dim3(km::NBLK * 4, (unsigned)B), dim3(256), 0, st, comp, dest, per_utt, D, (const float*)w, stride, masks);
-  else hipLaunchKernelGGL((kmeans2_mask_compact_kernel<0>), dim3(km::NBLK * 4, (unsigned)B), dim3(256), 0, st, comp, dest, per_utt, D, (const float*)w, stride, masks);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-int onssen_dc_cluster_f32(const float* emb, const float* feature, int B, int T, int F, int D, float db_threshold,
-                          int iters, float tol, float* masks, void* ws, size_t ws_bytes, int flags, void* stream) {
-  return dc_cluster_impl(emb, feature, B, T, F, D, db_threshold, iters, tol, masks, ws, ws_bytes, flags, stream, nullptr);
-}
-
-int onssen_dc_cluster_ragged_f32(const float* emb, const float* feature, int B, int T, const int32_t* frames, int F, int D,
-                                 float db_threshold, int iters, float tol, float* masks, void* ws, size_t ws_bytes, int flags,
-                                 void* stream) {
-  if (!frames) return ONSSEN_E_ARG;
-  return dc_cluster_impl(emb, feature, B, T, F, D, db_threshold, iters, tol, masks, ws, ws_bytes, flags, stream, frames);
 }
 
 #ifdef ONSSEN_FFT_PROFILE

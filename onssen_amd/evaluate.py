@@ -204,18 +204,16 @@ class tester_dc(tester):
         bit -- 1.35 x the utterances per second of the plain ``batch`` = 16 loop.  ``pipeline=False``, ``host_kmeans``, other models,
         modes or batch sizes: the plain loop -- also for every single forward whose ``sig_ref`` holds other than two sources (the
         pipeline is two-speaker; ``get_est_sig`` clusters into ``sig_ref.shape[1]`` speakers).  An aborted persistent launch re-runs
-        the forwards it touched on the plain loop's recovery path."""
-        import warnings
+        the forwards it touched on the plain loop's recovery path; the loop is ``separation.dc_stream``, so an estimate enters the
+        sum only after the status of the step that produced it has been examined."""
         from .nn._core import XcdAborted, _XcdPolicy, _XcdStatus
-        from .separation import DCRaggedPipeline
+        from .separation import DCRaggedPipeline, dc_stream
         K = int(batch)
         self.model = self.model.eval()
         F = getattr(self.model, "input_dim", 0)
         if not pipeline or self.host_kmeans or not 2 <= K <= 16 or DCRaggedPipeline.why_not(self.model, K, 2 * (F - 1)) is not None:
             return super().eval(window, batch, bucket)
         hop = self.hop_size
-        total, count = 0.0, 0
-        pipe, held = None, []          # held: the forwards whose estimate has not come back yet (at most 2)
 
         def plain(items, forced):
             import contextlib
@@ -227,70 +225,40 @@ class tester_dc(tester):
                     t, c = t + float(sdr.double().sum()), c + sdr.numel()
             return t, c
 
+        def fit(item, pipe):
+            (feature_mix,), label, _ = item
+            B, T, _ = feature_mix.shape
+            n = label[-1].shape[-1]
+            if label[-1].shape[1] != 2:           # the pipeline is two-speaker (DCRaggedPipeline): this forward takes the plain loop
+                return None
+            if pipe is not None and B == pipe.B and T <= pipe.T_cap and n <= pipe.n_cap:
+                return pipe
+            if DCRaggedPipeline.why_not(self.model, B, 2 * (F - 1)) is None:
+                return DCRaggedPipeline(self.model, B, int(1.25 * max(n, hop * T)), 2 * (F - 1), hop, 40.0)
+            return None                           # (a last, smaller chunk the pipeline cannot take)
+
+        def push(pipe, item):
+            (feature_mix,), label, (frames, lengths) = item
+            ri, sig_ref = _mix_ri(label)
+            return pipe.push_features(feature_mix, ri, frames, lengths, sig_ref.shape[-1])
+
         def settle(est, item):
             (_, label, (frames, lengths)) = item
             sdr = batch_SDR_torch(est, label[-1].float(), lengths=lengths)
             return float(sdr.double().sum()), sdr.numel()
 
-        def recover(e):
-            nonlocal held, pipe
-            _XcdPolicy.recovered += 1
-            warnings.warn(f"onssen_amd: {e}  Re-running {len(held)} forward(s) on the launch-per-step recurrence.", RuntimeWarning)
+        def rerun(held, e):
             try:
-                _XcdStatus.flush(policy=False)
+                _XcdStatus.flush(policy=False)    # the step's other launches ran into the same abort word: drain their reports
             except XcdAborted:
                 pass
-            if pipe:
-                pipe.reset()
-            t, c = plain(held, True)
-            held = []
-            return t, c
+            return [plain(held, True)]
 
-        def drain():
-            nonlocal held
-            if not (pipe and held):
-                return 0.0, 0
-            try:
-                est = pipe.flush()
-                t, c = settle(est, held[0])
-                held = []
-                return t, c
-            except XcdAborted as e:
-                return recover(e)
-
+        total, count = 0.0, 0
         with torch.no_grad():
-            for item in self._forwards(batch, bucket):
-                input, label, ragged = item
-                feature_mix, = input
-                ri, sig_ref = _mix_ri(label)
-                B, T, _ = feature_mix.shape
-                n = sig_ref.shape[-1]
-                if sig_ref.shape[1] != 2:         # the pipeline is two-speaker (DCRaggedPipeline): this forward takes the plain loop
-                    t, c = drain()
-                    total, count, pipe = total + t, count + c, None
-                    t, c = plain([item], False)
-                    total, count = total + t, count + c
-                    continue
-                if pipe is not None and (B != pipe.B or T > pipe.T_cap or n > pipe.n_cap):
-                    t, c = drain()
-                    total, count, pipe = total + t, count + c, None
-                if pipe is None and DCRaggedPipeline.why_not(self.model, B, 2 * (F - 1)) is None:
-                    pipe = DCRaggedPipeline(self.model, B, int(1.25 * max(n, hop * T)), 2 * (F - 1), hop, 40.0)
-                if pipe is None:                  # (a last, smaller chunk the pipeline cannot take)
-                    t, c = plain([item], False)
-                    total, count = total + t, count + c
-                    continue
-                held.append(item)
-                try:
-                    est = pipe.push_features(feature_mix, ri, ragged[0], ragged[1], n)
-                    if est is not None:
-                        t, c = settle(est, held.pop(0))
-                        total, count = total + t, count + c
-                except XcdAborted as e:
-                    t, c = recover(e)
-                    total, count = total + t, count + c
-            t, c = drain()
-            total, count = total + t, count + c
+            for t, c in dc_stream(self._forwards(batch, bucket), fit, push, settle, rerun, lambda item: plain([item], False),
+                                  "on the launch-per-step recurrence"):
+                total, count = total + t, count + c
         return total / max(count, 1)
 
     def get_est_sig(self, input, label, output, frames=None, lengths=None):

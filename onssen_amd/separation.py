@@ -225,6 +225,13 @@ def _cluster_ws(device, key, nb, head, ragged):
     return ws
 
 
+def _dc_compact_route(B, H, D):
+    """The compacted device-side clustering can end this forward: ``dc_cluster`` / ``dc_compact`` on, an embedding width the GEMM's
+    register epilogue holds, and a head GEMM that reads the recurrence's x3 image."""
+    from .nn._core import heads_take_image
+    return options.get("dc_cluster") == "1" and options.get("dc_compact") == "1" and D <= 32 and heads_take_image(B, H, (D,))
+
+
 def dc_masks_from_features(model, logmag, db_threshold=40.0, iters=20, frames=None, tol=1e-4):
     """Deep-clustering masks (B,T,F,2) straight from the mixture's log-magnitude WITHOUT materialising the embedding
     (round 4): the active bins are known before the network runs (evaluate.py:36-37), so the threshold is turned into a
@@ -236,16 +243,14 @@ def dc_masks_from_features(model, logmag, db_threshold=40.0, iters=20, frames=No
     Returns None when this forward cannot take that route (not an eval-mode ``deep_clustering`` on the persistent split-bf16
     path, an embedding width the GEMM's register epilogue does not hold, a forced launch-per-step re-run): the caller then
     computes the embedding and calls ``dc_masks``."""
-    import os
     from .hip import get_lib
-    from .nn._core import (_XcdPolicy, _XcdSerial, _XcdStatus, _stream, as_frames, heads_take_image, precision, run_blstm, use_hip_path)
+    from .nn._core import _XcdPolicy, _XcdSerial, _XcdStatus, as_frames, precision, run_blstm, use_hip_path
     from .nn.deep_clustering import deep_clustering
     B, T, F = logmag.shape
     D = getattr(model, "embedding_dim", 0)
     if (not isinstance(model, deep_clustering) or not use_hip_path(model) or F != model.input_dim or precision() == "f32"
-            or (frames is not None and precision() == "bf16")
-            or options.get("dc_cluster") != "1" or options.get("dc_compact") != "1"
-            or _XcdPolicy.force_steps != 0 or not heads_take_image(B, model.hidden_dim, (D,)) or D > 32):
+            or (frames is not None and precision() == "bf16") or _XcdPolicy.force_steps != 0
+            or not _dc_compact_route(B, model.hidden_dim, D)):
         return None
     lib = get_lib()
     logmag = logmag.float().contiguous()
@@ -295,8 +300,8 @@ def dc_masks(emb, logmag, db_threshold=40.0, iters=20, frames=None, tol=1e-4, nu
     ``frames`` (B,): a ragged batch -- utterance b owns its first frames[b] frames; its padding is never active, takes no
     part in the threshold or the sums, and gets zero masks.  Such calls (a new longest utterance per batch) share ONE
     grow-only workspace per device, allocated uninitialised with only its header zeroed."""
-    import os
     from . import _abi
+    from .features import _lengths_i32
     from .hip import get_lib
     from .nn._core import _XcdPolicy, _XcdSerial, _XcdStatus
     K = int(num_speaker)
@@ -305,15 +310,14 @@ def dc_masks(emb, logmag, db_threshold=40.0, iters=20, frames=None, tol=1e-4, nu
     lib = get_lib()
     B, T, F, D = emb.shape
     emb, logmag = emb.contiguous(), logmag.contiguous()
+    if frames is not None:
+        frames = _lengths_i32(frames, B, T, emb.device, "frames")
     if K > 2:
         nb = int(lib.dll.onssen_dc_cluster_k_workspace_bytes(B, T, F, D, K))
         if nb == 0:
             raise ValueError(f"dc_masks: unsupported shape for num_speaker = {K}: embedding {tuple(emb.shape)} (embedding_dim <= 32)")
         ws = _cluster_ws(emb.device, (emb.device, B, T, F, D, "k", K), nb, 0, frames is not None)      # (rewritten by every call)
         masks = torch.empty(B, T, F, K, device=emb.device, dtype=torch.float32)
-        if frames is not None:
-            from .features import _lengths_i32
-            frames = _lengths_i32(frames, B, T, emb.device, "frames")
         lib.dc_cluster_k(emb.data_ptr(), logmag.data_ptr(), B, T, F, D, K, float(db_threshold), iters, masks.data_ptr(),
                          ws.data_ptr(), nb, torch.cuda.current_stream().cuda_stream,
                          frames=frames.data_ptr() if frames is not None else None, tol=float(tol))
@@ -323,9 +327,6 @@ def dc_masks(emb, logmag, db_threshold=40.0, iters=20, frames=None, tol=1e-4, nu
     ws = _cluster_ws(emb.device, (emb.device, B, T, F, D), nb, head, frames is not None)
     persistent = options.get("dc_cluster") == "1" and _XcdPolicy.force_steps == 0
     masks = torch.empty(B, T, F, 2, device=emb.device, dtype=torch.float32)
-    if frames is not None:
-        from .features import _lengths_i32
-        frames = _lengths_i32(frames, B, T, emb.device, "frames")
     if persistent:
         _XcdSerial.before(emb.device)
     lib.dc_cluster(emb.data_ptr(), logmag.data_ptr(), B, T, F, D, float(db_threshold), iters, masks.data_ptr(),
@@ -390,7 +391,89 @@ def separate_dc(model, wav, window_size=256, hop_size=64, db_threshold=40.0, hos
     return mask_istft(ri, masks, hop_size, wav.shape[-1])
 
 
-class DCPipeline:
+def _dc_pipe_why_not(model, B, window_size, rows):
+    """None if this model / batch size / mode can run on a pipeline of at most ``rows`` rows (32 uniform, 16 ragged), else what
+    is missing (no allocation, no launch)."""
+    from .nn._core import _XcdPolicy, precision
+    from .nn.deep_clustering import deep_clustering
+    if not isinstance(model, deep_clustering) or model.num_layers != 2:
+        return "a deep_clustering model with num_layers = 2"
+    if model.training or next(model.parameters()).device.type != "cuda":
+        return "an eval-mode model on a ROCm device"
+    if window_size // 2 + 1 != model.input_dim:
+        return f"window_size // 2 + 1 == input_dim ({model.input_dim})"
+    if not 1 <= B <= rows or model.hidden_dim > 640:
+        return f"1 <= B <= {rows}{' (ragged rows run on stacked tiles)' if rows < 32 else ''} and hidden_dim <= 640"
+    if precision() != "bf16x3" or options.get("recurrence") != "1" or not _XcdPolicy.persistent_allowed():
+        return "the default split-bf16 arithmetic on the persistent recurrence"
+    if not _dc_compact_route(B, model.hidden_dim, model.embedding_dim):
+        return "the compacted device-side clustering (embedding_dim in 4, 8, 16, 20; dc_cluster / dc_compact on)"
+    return None
+
+
+class _DCPipeCore:
+    """What ``DCPipeline`` and ``DCRaggedPipeline`` share: the geometry, the two clustering workspaces (one per parity, headers
+    zeroed once) and the pair-launch workspace, the status posts, the drain's bookkeeping, and the back end of a step."""
+
+    def __init__(self, model, B, T, window_size, hop_size, db_threshold, iters, tol):
+        """``T``: the frames the workspaces are sized for."""
+        from . import _abi
+        from .hip import get_lib
+        self.model, self.lib, self.dev = model, get_lib(), next(model.parameters()).device
+        self.B, self.nfft, self.hop = int(B), int(window_size), int(hop_size)
+        self.F, self.D = window_size // 2 + 1, model.embedding_dim
+        self.db, self.iters, self.tol = float(db_threshold), int(iters), float(tol)
+        self.H, self.ug = model.hidden_dim, 4 * -(-model.hidden_dim // 128)
+        self.flags = _abi.BLSTM_BF16X3 | _abi.BLSTM_XCD
+        lib, F, D = self.lib, self.F, self.D
+        self.cnb, self.comp_off, self.dest_off = lib.dc_compact_layout(B, T, F, D)
+        self.cws = []
+        for _ in range(2):
+            w = torch.empty(self.cnb, dtype=torch.uint8, device=self.dev)
+            w[:self.comp_off].zero_()
+            self.cws.append(w)
+        self.cstat = int(lib.dll.onssen_dc_cluster_status_offset(B, D))
+        self.wnb = lib.blstm_pipe2_workspace_bytes(B, T, F, self.H, self.ug)
+        self.ws = torch.zeros(self.wnb, dtype=torch.uint8, device=self.dev)     # zeroed ONCE (ABI)
+        self.img_off, _ = lib.blstm_pipe2_y_image(B, T, F, self.H, self.ug)
+        self.count = 0               # batches pushed since the last reset
+
+    def _back_end(self, pk, q, T, comp_off, dest_off, ri, strides, n, out, st, frames=None, lengths=None):
+        """Head GEMM (active bins only, straight into the compacted array of parity ``q``), 2-means, masks and iSTFT of the batch
+        whose layer-1 output the pair launch has just left in ``ws``: T frames, spectrum ``ri``, ``n`` samples into ``out``."""
+        lib, B, F, D = self.lib, self.B, self.F, self.D
+        hd = self.model._head.get(pk.Hp)
+        cw = self.cws[q]
+        lib.linear_x3p_compact(self.ws.data_ptr() + self.img_off, T * B, 2 * pk.Hp, hd.img.data_ptr(), hd.b.data_ptr(), hd.N, D, 1e-12,
+                               cw.data_ptr() + dest_off, T * F, F, cw.data_ptr() + comp_off, B, T * F * D, False, st)
+        lib.dc_cluster_compact(B, T, F, D, self.iters, self.masks.data_ptr(), cw.data_ptr(), self.cnb, st, tol=self.tol)
+        lib.mask_istft(ri.data_ptr(), self.masks.data_ptr(), *strides, B, 2, T, self.nfft, self.hop, n, out.data_ptr(), st,
+                       frames=frames, lengths=lengths)
+
+    def _post(self, parities):
+        """Status words to examine: the pair launch's, and the clustering's of the parities whose back end ran."""
+        from .nn._core import _XcdStatus
+        _XcdStatus.post(self.ws)
+        for q in parities:
+            _XcdStatus.post_cluster(self.cws[q], self.cstat)
+
+    @torch.no_grad()
+    def flush(self):
+        """Drain: the separated LAST batch (or None if nothing is in flight); the pipeline is empty afterwards."""
+        from .nn._core import _XcdStatus
+        if self.count == 0:
+            return None
+        out = self._drain(self.count & 1)
+        self.count = 0
+        _XcdStatus.flush()
+        return out
+
+    def reset(self):
+        """Forget the batch in flight (after an aborted step: the exchange header was zeroed by the status poll)."""
+        self.count = 0
+
+
+class DCPipeline(_DCPipeCore):
     """Deep-clustering separation of a STREAM of equally shaped batches, software-pipelined over consecutive batches (round 6;
     the evaluation loop of onssen/utils/test.py:29-41 / egs/wsj0-2mix/deep_clustering/evaluate.py:31-45 hands over one batch after
     the other).  A two-layer BLSTM of <= 32 rows fills the chip's 8 XCDs only with 8-row recurrence groups, whose time step costs
@@ -412,52 +495,20 @@ class DCPipeline:
     Two speakers only (the compacted clustering it ends in is the 2-means): ``separate_dc(num_speaker=)`` separates three or four."""
 
     def __init__(self, model, B, n_samples, window_size=256, hop_size=64, db_threshold=40.0, iters=20, tol=1e-4, graph=True):
-        from . import _abi
-        from .hip import get_lib
-        from .nn._core import _XcdPolicy, _version_key, heads_take_image, precision
-        from .nn.deep_clustering import deep_clustering
-        dev = next(model.parameters()).device
-        D = getattr(model, "embedding_dim", 0)
-        F = window_size // 2 + 1
-        why = None
-        if not isinstance(model, deep_clustering) or model.num_layers != 2:
-            why = "a deep_clustering model with num_layers = 2"
-        elif model.training or dev.type != "cuda":
-            why = "an eval-mode model on a ROCm device"
-        elif F != model.input_dim:
-            why = f"window_size // 2 + 1 == input_dim ({model.input_dim})"
-        elif not 1 <= B <= 32 or model.hidden_dim > 640:
-            why = "1 <= B <= 32 and hidden_dim <= 640"
-        elif precision() != "bf16x3" or options.get("recurrence") != "1" or not _XcdPolicy.persistent_allowed():
-            why = "the default split-bf16 arithmetic on the persistent recurrence"
-        elif options.get("dc_cluster") != "1" or options.get("dc_compact") != "1" or D > 32 or not heads_take_image(B, model.hidden_dim, (D,)):
-            why = "the compacted device-side clustering (embedding_dim in 4, 8, 16, 20; dc_cluster / dc_compact on)"
+        from .nn._core import _version_key
+        why = _dc_pipe_why_not(model, B, window_size, 32)
         if why:
             raise RuntimeError(f"DCPipeline needs {why}; use separate_dc")
-        self.model, self.lib, self.dev = model, get_lib(), dev
-        self.B, self.n, self.nfft, self.hop = int(B), int(n_samples), int(window_size), int(hop_size)
-        self.T, self.F, self.D = 1 + self.n // self.hop, F, D
-        self.db, self.iters, self.tol = float(db_threshold), int(iters), float(tol)
-        self.H, self.ug = model.hidden_dim, 4 * -(-model.hidden_dim // 128)
-        self.flags = _abi.BLSTM_BF16X3 | _abi.BLSTM_XCD
-        lib, T = self.lib, self.T
+        self.n = int(n_samples)
+        self.T = T = 1 + self.n // int(hop_size)
+        super().__init__(model, B, T, window_size, hop_size, db_threshold, iters, tol)
+        dev, F = self.dev, self.F
         mk = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
         self.wav = [torch.zeros(B, self.n, device=dev) for _ in range(2)]
         self.logmag = [mk(B, T, F) for _ in range(2)]
         self.ri = [mk(B, T, F, 2) for _ in range(2)]
         self.out = [torch.zeros(B, 2, self.n, device=dev) for _ in range(2)]
         self.masks = mk(B, T, F, 2)
-        self.cnb, self.comp_off, self.dest_off = lib.dc_compact_layout(B, T, F, D)
-        self.cws = []
-        for _ in range(2):
-            w = torch.empty(self.cnb, dtype=torch.uint8, device=dev)
-            w[:self.comp_off].zero_()
-            self.cws.append(w)
-        self.cstat = int(lib.dll.onssen_dc_cluster_status_offset(B, D))
-        self.wnb = lib.blstm_pipe2_workspace_bytes(B, T, F, self.H, self.ug)
-        self.ws = torch.zeros(self.wnb, dtype=torch.uint8, device=dev)          # zeroed ONCE (ABI)
-        self.img_off, _ = lib.blstm_pipe2_y_image(B, T, F, self.H, self.ug)
-        self.count = 0               # batches pushed since the last reset
         self.graphs = [None, None]
         self.use_graph = bool(graph)
         self._wkey = None
@@ -466,26 +517,19 @@ class DCPipeline:
 
     # -- one pipeline step on the current stream: buffers of parity p take batch n, those of 1 - p hold batch n - 1
     def _enqueue(self, p, back_end=True):
-        lib, B, T, F, D = self.lib, self.B, self.T, self.F, self.D
+        lib, B, T, F = self.lib, self.B, self.T, self.F
         st = torch.cuda.current_stream().cuda_stream
         pk = self.model._packed.get(self.ug)
-        hd = self.model._head.get(pk.Hp)
-        q = 1 - p
         lib.stft_logmag(self.wav[p].data_ptr(), B, self.n, self.n, self.nfft, self.hop, 1e-7, self.logmag[p].data_ptr(),
                         self.ri[p].data_ptr(), st)
-        lib.dc_index(self.logmag[p].data_ptr(), B, T, F, D, self.db, self.cws[p].data_ptr(), self.cnb, st)
+        lib.dc_index(self.logmag[p].data_ptr(), B, T, F, self.D, self.db, self.cws[p].data_ptr(), self.cnb, st)
         lib.blstm_pipe2_forward(self.logmag[p].data_ptr(), T * F, F, B, T, F, self.H, self.ug,
                                 [t.data_ptr() for t in pk.wih_img], [t.data_ptr() for t in pk.whh_x3], [t.data_ptr() for t in pk.bias],
                                 self.ws.data_ptr(), self.wnb, self.flags, st)
-        if not back_end:
-            return
-        cw = self.cws[q]
-        lib.linear_x3p_compact(self.ws.data_ptr() + self.img_off, T * B, 2 * pk.Hp, hd.img.data_ptr(), hd.b.data_ptr(), hd.N, D, 1e-12,
-                               cw.data_ptr() + self.dest_off, T * F, F, cw.data_ptr() + self.comp_off, B, T * F * D, False, st)
-        lib.dc_cluster_compact(B, T, F, D, self.iters, self.masks.data_ptr(), cw.data_ptr(), self.cnb, st, tol=self.tol)
-        m = self.masks
-        lib.mask_istft(self.ri[q].data_ptr(), m.data_ptr(), m.stride(0), m.stride(3), m.stride(1), m.stride(2), B, 2, T, self.nfft,
-                       self.hop, self.n, self.out[p].data_ptr(), st)
+        if back_end:
+            m = self.masks
+            self._back_end(pk, 1 - p, T, self.comp_off, self.dest_off, self.ri[1 - p], (m.stride(0), m.stride(3), m.stride(1), m.stride(2)),
+                           self.n, self.out[p], st)
 
     def _prime(self):
         """Two eager steps on silence: every kernel has run once, both target maps and the layer-1 projection hold finite data."""
@@ -493,14 +537,8 @@ class DCPipeline:
         _XcdStatus.poll()
         for p in (0, 1):
             self._enqueue(p, back_end=p == 1)
-        self._post()
+        self._post((0, 1))
         self.count = 0
-
-    def _post(self):
-        from .nn._core import _XcdStatus
-        _XcdStatus.post(self.ws)
-        for w in self.cws:
-            _XcdStatus.post_cluster(w, self.cstat)
 
     def _capture(self):
         key = self._version_key(self.model.rnn.flat_weights() + [self.model.fc_dc.weight, self.model.bn.running_mean])
@@ -555,32 +593,20 @@ class DCPipeline:
         else:
             self.step(p)
         if check:
-            self._post()
+            self._post((0, 1))
         self.count += 1
         return self.out[p] if self.count > 1 else None
 
-    @torch.no_grad()
-    def flush(self):
-        """Drain: the separated LAST batch (or None if nothing is in flight); the pipeline is empty afterwards."""
-        from .nn._core import _XcdStatus
-        if self.count == 0:
-            return None
-        p = self.count & 1
+    def _drain(self, p):
         self.wav[p].zero_()
         if self.use_graph:
             self._capture()
         self.step(p)
-        self._post()
-        self.count = 0
-        _XcdStatus.flush()
+        self._post((0, 1))
         return self.out[p]
 
-    def reset(self):
-        """Forget the batch in flight (after an aborted step: the exchange header was zeroed by the status poll)."""
-        self.count = 0
 
-
-class DCRaggedPipeline:
+class DCRaggedPipeline(_DCPipeCore):
     """``DCPipeline`` for a stream of RAGGED batches of whole utterances (round 6c) -- the shape the reference evaluates one by one
     (onssen/utils/test.py:29-41) and ``separate_dc(..., lengths=)`` runs K at a time: every batch is B <= 16 rows padded to ITS OWN
     longest utterance.  A ragged batch of <= 16 rows runs on stacked 4-row recurrence groups, whose time step costs what an 8-row
@@ -598,67 +624,31 @@ class DCRaggedPipeline:
     @staticmethod
     def why_not(model, B, window_size=256):
         """None if this model / batch size / mode can run here, else what is missing (no allocation, no launch)."""
-        from .nn._core import _XcdPolicy, heads_take_image, precision
-        from .nn.deep_clustering import deep_clustering
-        if not isinstance(model, deep_clustering) or model.num_layers != 2:
-            return "a deep_clustering model with num_layers = 2"
-        dev = next(model.parameters()).device
-        D = getattr(model, "embedding_dim", 0)
-        if model.training or dev.type != "cuda":
-            return "an eval-mode model on a ROCm device"
-        if window_size // 2 + 1 != model.input_dim:
-            return f"window_size // 2 + 1 == input_dim ({model.input_dim})"
-        if not 1 <= B <= 16 or model.hidden_dim > 640:
-            return "1 <= B <= 16 (ragged rows run on stacked tiles) and hidden_dim <= 640"
-        if precision() != "bf16x3" or options.get("recurrence") != "1" or not _XcdPolicy.persistent_allowed():
-            return "the default split-bf16 arithmetic on the persistent recurrence"
-        if options.get("dc_cluster") != "1" or options.get("dc_compact") != "1" or D > 32 or not heads_take_image(B, model.hidden_dim, (D,)):
-            return "the compacted device-side clustering (embedding_dim in 4, 8, 16, 20; dc_cluster / dc_compact on)"
-        return None
+        return _dc_pipe_why_not(model, B, window_size, 16)
 
     def __init__(self, model, B, n_cap, window_size=256, hop_size=64, db_threshold=40.0, iters=20, tol=1e-4):
-        from . import _abi
-        from .hip import get_lib
-        dev = next(model.parameters()).device
-        D = getattr(model, "embedding_dim", 0)
-        F = window_size // 2 + 1
         why = self.why_not(model, B, window_size)
         if why is None and n_cap < hop_size:
             why = "n_cap >= hop_size"
         if why:
             raise RuntimeError(f"DCRaggedPipeline needs {why}; use separate_dc(..., lengths=)")
-        self.model, self.lib, self.dev = model, get_lib(), dev
-        self.B, self.n_cap, self.nfft, self.hop = int(B), int(n_cap), int(window_size), int(hop_size)
-        self.T_cap, self.F, self.D = 1 + self.n_cap // self.hop, F, D
-        self.db, self.iters, self.tol = float(db_threshold), int(iters), float(tol)
-        self.H, self.ug = model.hidden_dim, 4 * -(-model.hidden_dim // 128)
-        self.flags = _abi.BLSTM_BF16X3 | _abi.BLSTM_XCD
-        lib, T = self.lib, self.T_cap
+        self.n_cap = int(n_cap)
+        self.T_cap = T = 1 + self.n_cap // int(hop_size)
+        super().__init__(model, B, T, window_size, hop_size, db_threshold, iters, tol)
+        dev, F = self.dev, self.F
         mk = lambda k: torch.empty(k, device=dev, dtype=torch.float32)
         self.logmag = [torch.zeros(B * T * F, device=dev) for _ in range(2)]
         self.ri = [mk(B * T * F * 2) for _ in range(2)]
         self.out = [mk(B * 2 * self.n_cap) for _ in range(2)]
         self.masks = mk(B * T * F * 2)
-        self.cnb, self.comp_off, _ = lib.dc_compact_layout(B, T, F, D)
-        self.cws = []
-        for _ in range(2):
-            w = torch.empty(self.cnb, dtype=torch.uint8, device=dev)
-            w[:self.comp_off].zero_()
-            self.cws.append(w)
-        self.cstat = int(lib.dll.onssen_dc_cluster_status_offset(B, D))
-        self.wnb = lib.blstm_pipe2_workspace_bytes(B, T, F, self.H, self.ug)
-        self.ws = torch.zeros(self.wnb, dtype=torch.uint8, device=dev)          # zeroed ONCE (ABI)
-        self.img_off, _ = lib.blstm_pipe2_y_image(B, T, F, self.H, self.ug)
-        self.meta = [None, None]     # per parity: (T, n, frames, lengths) of the batch its buffers hold
-        self.count = 0
+        self.meta = [None, None]     # per parity: (T, n, frames, lengths, logmag, ri) of the batch its buffers hold
 
     def _step(self, p, cur, back_end):
         """The pair launch for the batch ``cur`` = (T, n, frames, lengths, logmag, ri) beside the batch of parity 1 - p, then
-        (``back_end``) that batch's head GEMM, clustering, masks and iSTFT into ``out[p]``."""
-        lib, B, F, D = self.lib, self.B, self.F, self.D
+        (``back_end``) that batch's head GEMM, clustering, masks and iSTFT into ``out[p]``; the status posts."""
+        lib, B, F = self.lib, self.B, self.F
         st = torch.cuda.current_stream().cuda_stream
         pk = self.model._packed.get(self.ug)
-        hd = self.model._head.get(pk.Hp)
         q = 1 - p
         T, n, frames, lengths, x, _ = cur
         Tq, nq, frames_q, lengths_q, _, ri_q = self.meta[q] if back_end else cur
@@ -667,20 +657,10 @@ class DCRaggedPipeline:
                                        [t.data_ptr() for t in pk.bias], self.ws.data_ptr(), self.wnb, self.flags, st)
         if not back_end:
             return None
-        cw = self.cws[q]
-        _, comp_off, dest_off = lib.dc_compact_layout(B, Tq, F, D)
-        lib.linear_x3p_compact(self.ws.data_ptr() + self.img_off, Tq * B, 2 * pk.Hp, hd.img.data_ptr(), hd.b.data_ptr(), hd.N, D, 1e-12,
-                               cw.data_ptr() + dest_off, Tq * F, F, cw.data_ptr() + comp_off, B, Tq * F * D, False, st)
-        lib.dc_cluster_compact(B, Tq, F, D, self.iters, self.masks.data_ptr(), cw.data_ptr(), self.cnb, st, tol=self.tol)
-        lib.mask_istft(ri_q.data_ptr(), self.masks.data_ptr(), Tq * F * 2, 1, F * 2, 2, B, 2, Tq, self.nfft, self.hop, nq,
-                       self.out[p].data_ptr(), st, frames=frames_q.data_ptr(), lengths=lengths_q.data_ptr())
+        _, comp_off, dest_off = lib.dc_compact_layout(B, Tq, F, self.D)
+        self._back_end(pk, q, Tq, comp_off, dest_off, ri_q, (Tq * F * 2, 1, F * 2, 2), nq, self.out[p], st,
+                       frames_q.data_ptr(), lengths_q.data_ptr())
         return self.out[p][:B * 2 * nq].view(B, 2, nq)
-
-    def _post(self, q, back_end):
-        from .nn._core import _XcdStatus
-        _XcdStatus.post(self.ws)
-        if back_end:
-            _XcdStatus.post_cluster(self.cws[q], self.cstat)
 
     def _advance(self, cur, check):
         """Target map of ``cur`` (the features are in place), the pipeline step, the status posts."""
@@ -692,7 +672,7 @@ class DCRaggedPipeline:
         out = self._step(p, cur, back_end)
         self.meta[p] = cur
         if check:
-            self._post(1 - p, back_end)
+            self._post((1 - p,) if back_end else ())
         self.count += 1
         return out
 
@@ -739,24 +719,70 @@ class DCRaggedPipeline:
             _XcdStatus.poll()
         return self._advance((T, int(n), frames, lengths, logmag, stft_ri), check)
 
-    @torch.no_grad()
-    def flush(self):
-        """Drain: the separated LAST batch (or None if nothing is in flight); the pipeline is empty afterwards."""
-        from .nn._core import _XcdStatus
-        if self.count == 0:
-            return None
-        p = self.count & 1
-        q = 1 - p
+    def _drain(self, p):
         # the launch's other half needs SOME batch: the last one's own features again (its layer-0 output is not used)
-        out = self._step(p, self.meta[q], True)
-        self._post(q, True)
-        self.count = 0
-        _XcdStatus.flush()
+        out = self._step(p, self.meta[1 - p], True)
+        self._post((1 - p,))
         return out
 
-    def reset(self):
-        """Forget the batch in flight (after an aborted step: the exchange header was zeroed by the status poll)."""
-        self.count = 0
+
+def dc_stream(items, fit, push, release, rerun, fallback, how):
+    """The loop behind ``separate_dc_stream``, ``separate_dc_ragged_stream`` and ``tester_dc.eval``: generator of one result per item
+    of ``items``, in order, through a pipeline that returns item k-1's estimate when item k is pushed.  At most two items are held
+    (pushed, result not released yet); the order per item is push -> compute the result -> ``_XcdStatus.flush()`` -> release, so a
+    result whose step gave up a bounded wait (``XcdAborted``, from the push, the flush or that status check) is never released:
+    the recovery counts ``_XcdPolicy.recovered``, warns, resets the pipeline and re-runs everything held.  What differs per caller:
+
+      fit(item, pipe)     the pipeline that takes ``item``: ``pipe`` itself, another one (the held items are drained through
+                          ``pipe.flush()`` first), or None -- the item then goes through ``fallback(item)`` after the same drain
+      push(pipe, item)    hand the item over; the previous item's estimate, or None
+      release(est, item)  what the estimate ``est`` of ``item`` becomes (a clone; its SI-SDR sum): computed before the status check
+      rerun(held, e)      the results (a list) of the held items after the abort ``e``, without the pipeline
+      how                 the end of the warning: how ``rerun`` does it."""
+    import warnings
+    from .nn._core import XcdAborted, _XcdPolicy, _XcdStatus
+    pipe, held = None, []
+
+    def recover(e):
+        nonlocal held
+        _XcdPolicy.recovered += 1
+        warnings.warn(f"onssen_amd: {e}  Re-running {len(held)} batch(es) of that pipeline step {how}.", RuntimeWarning)
+        pipe.reset()
+        todo, held = held, []
+        return rerun(todo, e)
+
+    def drain():
+        nonlocal held
+        if not held:
+            return []
+        try:
+            res = release(pipe.flush(), held[0])       # (flush() examines the status itself)
+            held = []
+            return [res]
+        except XcdAborted as e:
+            return recover(e)
+
+    for item in items:
+        fitted = fit(item, pipe)
+        if fitted is not pipe:
+            yield from drain()
+            pipe = fitted
+        if pipe is None:
+            yield fallback(item)
+            continue
+        held.append(item)
+        try:
+            est = push(pipe, item)
+            if est is None:
+                continue
+            res = release(est, held[0])
+            _XcdStatus.flush()                 # the step that produced it has completed cleanly (the next one is not enqueued yet)
+            held.pop(0)
+        except XcdAborted as e:
+            yield from recover(e)
+            continue
+        yield res
+    yield from drain()
 
 
 @torch.no_grad()
@@ -766,103 +792,39 @@ def separate_dc_ragged_stream(model, batches, window_size=256, hop_size=64, db_t
     result per batch, in order (a fresh tensor each), bit for bit what ``separate_dc`` returns for it.  The pipeline's buffers are
     sized for the longest batch seen so far (a longer one drains it and starts a larger one); a batch it cannot take (another B,
     more than 16 rows, a model or mode ``DCRaggedPipeline`` refuses) goes through ``separate_dc``; a step whose persistent launch
-    gave up a bounded wait is recovered by separating the batches it touched again with ``separate_dc``."""
-    import warnings
-    from .nn._core import XcdAborted, _XcdPolicy, _XcdStatus
-    pipe, held = None, []                      # held: (wav, lengths) whose result has not been yielded yet (at most 2)
-    sep = lambda w, l: separate_dc(model, w, window_size, hop_size, db_threshold, lengths=l)
+    gave up a bounded wait is recovered by separating the batches it touched again with ``separate_dc`` (``dc_stream``)."""
+    sep = lambda item: separate_dc(model, item[0], window_size, hop_size, db_threshold, lengths=item[1])
 
-    def drain():
-        nonlocal held
-        if pipe and held:
-            try:
-                res = pipe.flush().clone()
-                held = []
-                return [res]
-            except XcdAborted as e:
-                _XcdPolicy.recovered += 1
-                warnings.warn(f"onssen_amd: {e}  Re-running the last batch with separate_dc.", RuntimeWarning)
-                pipe.reset()
-        res = [sep(w, l) for w, l in held[-1:]] if pipe else []
-        held = []
-        return res
-
-    for wav, lengths in batches:
-        B, n = wav.shape
-        if pipe is not None and pipe is not False and (B != pipe.B or n > pipe.n_cap):
-            yield from drain()
-            pipe = None
-        if pipe is None:
-            try:
-                pipe = DCRaggedPipeline(model, B, int(n * 1.25) if B <= 16 else n, window_size, hop_size, db_threshold)
-            except RuntimeError:
-                pipe = False
-        if pipe is False:
-            yield sep(wav, lengths)
-            pipe = None
-            continue
-        held.append((wav, lengths))
+    def fit(item, pipe):
+        B, n = item[0].shape
+        if pipe is not None and B == pipe.B and n <= pipe.n_cap:
+            return pipe
         try:
-            out = pipe.push(wav, lengths)
-            if out is not None:
-                res = out.clone()
-                _XcdStatus.flush()             # the step that produced it has completed cleanly (the next one is not enqueued yet)
-                held.pop(0)
-                yield res
-        except XcdAborted as e:
-            _XcdPolicy.recovered += 1
-            warnings.warn(f"onssen_amd: {e}  Re-running the batches of that pipeline step with separate_dc.", RuntimeWarning)
-            pipe.reset()
-            for w, l in held:
-                yield sep(w, l)
-            held = []
-    yield from drain()
+            return DCRaggedPipeline(model, B, int(n * 1.25) if B <= 16 else n, window_size, hop_size, db_threshold)
+        except RuntimeError:
+            return None
+
+    yield from dc_stream(batches, fit, lambda pipe, item: pipe.push(*item), lambda est, item: est.clone(),
+                         lambda held, e: [sep(item) for item in held], sep, "with separate_dc")
 
 
 @torch.no_grad()
 def separate_dc_stream(model, batches, window_size=256, hop_size=64, db_threshold=40.0, graph=True):
     """Generator: ``separate_dc`` over an iterable of equally shaped (B, n) device batches, through ``DCPipeline`` -- yields one
     (B, 2, n) result per batch, in order (a fresh tensor each).  A step whose persistent launch gave up a bounded wait is
-    recovered here: the two batches it touched are separated again with ``separate_dc`` and the pipeline restarts.  Batches
-    the pipeline cannot take (see DCPipeline) go through ``separate_dc`` one by one."""
-    import warnings
-    from .nn._core import XcdAborted, _XcdPolicy, _XcdStatus
-    pipe, held = None, []                      # held: inputs whose result has not been yielded yet (at most 2)
-    for wav in batches:
-        if pipe is None:
+    recovered (``dc_stream``): the batches it touched are separated again with ``separate_dc`` and the pipeline restarts.  Batches
+    the pipeline cannot take (see DCPipeline; another shape than the first batch's) go through ``separate_dc`` one by one, after
+    the batch in flight has been drained."""
+    sep = lambda wav: separate_dc(model, wav, window_size, hop_size, db_threshold)
+    made = []                                  # the ONE pipeline of this stream, sized for the first batch; False: refused
+
+    def fit(wav, pipe):
+        if not made:
             try:
-                pipe = DCPipeline(model, wav.shape[0], wav.shape[1], window_size, hop_size, db_threshold, graph=graph)
+                made.append(DCPipeline(model, wav.shape[0], wav.shape[1], window_size, hop_size, db_threshold, graph=graph))
             except RuntimeError:
-                pipe = False
-        if pipe is False or tuple(wav.shape) != (pipe.B, pipe.n):
-            for h in held:                     # (a shape change: drain what is in flight first)
-                yield separate_dc(model, h, window_size, hop_size, db_threshold)
-            held = []
-            if pipe:
-                pipe.reset()
-            yield separate_dc(model, wav, window_size, hop_size, db_threshold)
-            continue
-        held.append(wav)
-        try:
-            out = pipe.push(wav)
-            if out is not None:
-                res = out.clone()
-                _XcdStatus.flush()             # the step that produced it has completed cleanly (the next one is not enqueued yet)
-                held.pop(0)
-                yield res
-        except XcdAborted as e:
-            _XcdPolicy.recovered += 1
-            warnings.warn(f"onssen_amd: {e}  Re-running the batches of that pipeline step with separate_dc.", RuntimeWarning)
-            pipe.reset()
-            for h in held:
-                yield separate_dc(model, h, window_size, hop_size, db_threshold)
-            held = []
-    if pipe and held:
-        try:
-            res = pipe.flush().clone()
-            yield res
-        except XcdAborted as e:
-            _XcdPolicy.recovered += 1
-            warnings.warn(f"onssen_amd: {e}  Re-running the last batch with separate_dc.", RuntimeWarning)
-            pipe.reset()
-            yield separate_dc(model, held[-1], window_size, hop_size, db_threshold)
+                made.append(False)
+        return made[0] if made[0] and tuple(wav.shape) == (made[0].B, made[0].n) else None
+
+    yield from dc_stream(batches, fit, lambda pipe, wav: pipe.push(wav), lambda est, wav: est.clone(),
+                         lambda held, e: [sep(wav) for wav in held], sep, "with separate_dc")
