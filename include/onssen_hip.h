@@ -571,6 +571,29 @@ int onssen_loss_phase_grad_f32(const float* mask_a, const float* mask_b, int64_t
                                const float* phase_s1, const float* phase_s2, int B, int TF, const float* g_mask,
                                const float* g_phase, const int32_t* perm, float* d_mask_a, float* d_mask_b, int64_t d_sb,
                                int64_t d_se, float* d_phase_a, float* d_phase_b, void* stream);
+/* Speech enhancement (egs/daps), csrc/enhance.inc.
+ * onssen_labels_enhance_f32: the label maps of onssen/data/daps_enhance.py:104-106 in one pass over the two (n_bins, 2) spectra
+ * (contiguous, 8-byte aligned): mag_noisy = hypotf(Re X, Im X), mag_clean likewise, cos_diff = cosf(atan2f(X) - atan2f(S)) -- the
+ * bits of onssen_cos_difference_f32(stft_noisy, stft_clean).  cos_diff may be NULL (evaluation needs the magnitudes only);
+ * stft_clean, mag_clean and cos_diff may all three be NULL (separation has the noisy spectrum only: mag_noisy alone).
+ * onssen_loss_enhance_f32: onssen/loss/loss_mask.py, `mode` selecting the loss; every map (B, TF) contiguous:
+ *   ONSSEN_ENHANCE_MSA  per_utt[b] = sum_bins (est - mag_clean)^2                       (mag_noisy, cos_diff unused: may be NULL)
+ *   ONSSEN_ENHANCE_PSA  per_utt[b] = sum_bins |est * mag_noisy - t|,  t = min(mag_noisy, relu(mag_clean * cos_diff))   (est: the mask)
+ *   total[0] = scale * sum_b per_utt[b]  (nullable; MSELoss's mean is scale = 1 / (B * TF)).
+ * Per-bin terms in fp32 (the PSA residual is one fused multiply-add), sums in fp64 in a fixed order (no atomics:
+ * bit-repeatable).  ws: caller-owned, 8-byte aligned, onssen_loss_enhance_workspace_bytes(B) bytes, needs no zeroing.
+ * onssen_loss_enhance_grad_f32, one elementwise pass, d_est (B, TF) contiguous:
+ *   MSA  d_est = g[0] * 2 * scale * (est - mag_clean)            (g: the incoming gradient of total, one float)
+ *   PSA  d_est = g[b] * mag_noisy * sign(est * mag_noisy - t)    (g: the incoming gradient of per_utt, B floats; sign(0) = 0) */
+#define ONSSEN_ENHANCE_MSA 0
+#define ONSSEN_ENHANCE_PSA 1
+int onssen_labels_enhance_f32(const float* stft_noisy, const float* stft_clean, int64_t n_bins, float* mag_noisy, float* mag_clean,
+                              float* cos_diff, void* stream);
+size_t onssen_loss_enhance_workspace_bytes(int B);
+int onssen_loss_enhance_f32(int mode, const float* est, const float* mag_noisy, const float* mag_clean, const float* cos_diff, int B,
+                            int TF, float scale, float* per_utt, float* total, void* ws, size_t ws_bytes, void* stream);
+int onssen_loss_enhance_grad_f32(int mode, const float* est, const float* mag_noisy, const float* mag_clean, const float* cos_diff,
+                                 int B, int TF, float scale, const float* g, float* d_est, void* stream);
 size_t onssen_loss_dc_workspace_bytes(int B);
 int onssen_loss_dc_f32(const float* emb, const float* one_hot, const float* mag, int B, int TF, int D, int C,
                        float* per_utt, float* total_mag, void* ws, size_t ws_bytes, void* stream);
@@ -654,6 +677,16 @@ int onssen_mask_istft_f32(const float* stft_ri, const float* mask, int64_t m_sb,
 int onssen_phase_istft_f32(const float* stft_ri, const float* mask, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf,
                            const float* phase, int64_t p_sc, int B, int C, int T, int n_fft, int hop, int length, float* out,
                            void* stream);
+/* The same from an estimated MAGNITUDE with the mixture's phase (enhancement's reconstruction): `mag` (strided like `mask`, not
+ * NULL) and the spectrum at a bin is
+ *   mag * X / |X|,  |X| = hypotf(Re X, Im X) and both quotients in float32, the product in fp64; (1, 0) for X / |X| where X = 0
+ * (np.angle(0) = 0).  Any C (one transform per channel); n_fft in {256, 512, 1024}.  The ragged form takes `frames` and
+ * `lengths` exactly as onssen_mask_istft_ragged_f32 below. */
+int onssen_mag_istft_f32(const float* stft_ri, const float* mag, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf, int B,
+                         int C, int T, int n_fft, int hop, int length, float* out, void* stream);
+int onssen_mag_istft_ragged_f32(const float* stft_ri, const float* mag, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf,
+                                int B, int C, int T, const int32_t* frames, int n_fft, int hop, int length, const int32_t* lengths,
+                                float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Ragged batches (round 4): the reference evaluates WHOLE utterances one at a time (onssen/utils/test.py:29-41 with the

@@ -9,6 +9,7 @@ import ctypes as C
 import os
 
 EPI_BIAS, EPI_L2NORM, EPI_SIGMOID, EPI_RELU = 0, 1, 2, 3
+ENHANCE_MSA, ENHANCE_PSA = 0, 1   # ONSSEN_ENHANCE_*: the `mode` of onssen_loss_enhance_f32 / _grad_f32
 EPI_BF16 = 0x100   # OR-ed into the mode of linear_x3p: plain bf16 products
 ABI_VERSION = 14
 WAV_TRUNCATED = 1
@@ -108,6 +109,10 @@ SIGNATURES = {
     "onssen_loss_phase_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "onssen_loss_phase_grad_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                         _i64, _i64, _vp, _vp, _vp]),
+    "onssen_labels_enhance_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "onssen_loss_enhance_workspace_bytes": (_sz, [_i]),
+    "onssen_loss_enhance_f32": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "onssen_loss_enhance_grad_f32": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
     "onssen_loss_dc_workspace_bytes": (_sz, [_i]),
     "onssen_batch_sdr_workspace_bytes": (_sz, [_i]),
     "onssen_batch_sdr_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -117,6 +122,8 @@ SIGNATURES = {
     "onssen_dc_cluster_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _sz, _i, _vp]),
     "onssen_mask_istft_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "onssen_phase_istft_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "onssen_mag_istft_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "onssen_mag_istft_ragged_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     # deep-clustering separation without the embedding round trip (round 4)
     "onssen_dc_compact_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "onssen_dc_compact_layout": (_i, [_i, _i, _i, _i, _vp, _vp]),
@@ -613,6 +620,29 @@ class Lib:
     def phase_istft(self, stft_ri, mask, m_sb, m_sc, m_st, m_sf, phase, p_sc, B, Cn, T, n_fft, hop, length, out, stream):
         self.check(self.dll.onssen_phase_istft_f32(stft_ri, mask, m_sb, m_sc, m_st, m_sf, phase, p_sc, B, Cn, T, n_fft, hop,
                                                    length, out, stream), "onssen_phase_istft_f32")
+
+    def mag_istft(self, stft_ri, mag, m_sb, m_sc, m_st, m_sf, B, Cn, T, n_fft, hop, length, out, stream, frames=None, lengths=None):
+        if frames is not None:       # ragged batch, as mask_istft
+            self.check(self.dll.onssen_mag_istft_ragged_f32(stft_ri, mag, m_sb, m_sc, m_st, m_sf, B, Cn, T, frames, n_fft, hop,
+                                                            length, lengths, out, stream), "onssen_mag_istft_ragged_f32")
+            return
+        self.check(self.dll.onssen_mag_istft_f32(stft_ri, mag, m_sb, m_sc, m_st, m_sf, B, Cn, T, n_fft, hop, length, out, stream),
+                   "onssen_mag_istft_f32")
+
+    def labels_enhance(self, noisy, clean, n_bins, mag_noisy, mag_clean, cos_diff, stream):
+        self.check(self.dll.onssen_labels_enhance_f32(noisy, clean, n_bins, mag_noisy, mag_clean, cos_diff, stream),
+                   "onssen_labels_enhance_f32")
+
+    def loss_enhance_workspace_bytes(self, B):
+        return int(self.dll.onssen_loss_enhance_workspace_bytes(B))
+
+    def loss_enhance(self, mode, est, mag_noisy, mag_clean, cos_diff, B, TF, scale, per_utt, total, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_loss_enhance_f32(mode, est, mag_noisy, mag_clean, cos_diff, B, TF, scale, per_utt, total, ws,
+                                                    ws_bytes, stream), "onssen_loss_enhance_f32")
+
+    def loss_enhance_grad(self, mode, est, mag_noisy, mag_clean, cos_diff, B, TF, scale, g, d_est, stream):
+        self.check(self.dll.onssen_loss_enhance_grad_f32(mode, est, mag_noisy, mag_clean, cos_diff, B, TF, scale, g, d_est, stream),
+                   "onssen_loss_enhance_grad_f32")
 
     def phase_input(self, x_mag, mask, m_sb, m_sc, m_st, m_sf, x_phase, B, Cn, T, F, out, stream):
         self.check(self.dll.onssen_phase_input_f32(x_mag, mask, m_sb, m_sc, m_st, m_sf, x_phase, B, Cn, T, F, out,

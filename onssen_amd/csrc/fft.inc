@@ -290,14 +290,21 @@ __global__ __launch_bounds__(256) void stft_logmag_kernel(const float* __restric
 // PHASE (phase_net's reconstruction, onssen_phase_istft_f32): speaker c's operand at a bin is mask_c * |X| * (p_c.re, p_c.im) with
 // the network's unit phase vector p_c instead of X * mask_c; p_c (B,T,F,2) sits at phase + c * p_sc.  |X| = hypotf(Re X, Im X) in
 // float32, as the reference's np.abs of a complex64 spectrum; the phases ride in the same batch of loads as the masks.
+// MAG (enhancement's reconstruction, onssen_mag_istft_f32): `mask` holds an estimated MAGNITUDE m and the operand at a bin is
+// m * X / |X| -- that magnitude with the mixture's phase.  |X| = hypotf(Re X, Im X) and the two quotients are float32, the product
+// with m is fp64 like PHASE's; a bin with X = 0 takes the unit vector (1, 0), as exp(i np.angle(0)) = 1.  Unpaired only (one
+// estimate per input).
+enum { ISTFT_MASK = 0, ISTFT_PHASE = 1, ISTFT_MAG = 2 };
 __device__ const float kIstftOne = 1.0f;
-template <int N, int FB, bool PAIR, bool PHASE>
+template <int N, int FB, bool PAIR, int MODE>
 __global__ __launch_bounds__(256) void mask_istft_kernel(const float* __restrict__ stft_ri,
                                                          const float* __restrict__ mask, long m_sb, long m_sc,
                                                          long m_st, long m_sf, int C, int T, int hop, int length,
                                                          int FR, float* __restrict__ out,
                                                          const int* __restrict__ frames, const int* __restrict__ lengths,
                                                          const float* __restrict__ phase, long p_sc) {
+  constexpr bool PHASE = MODE == ISTFT_PHASE, MAG = MODE == ISTFT_MAG;
+  static_assert(!(MAG && PAIR), "the magnitude form is unpaired");
   constexpr int NS = PAIR ? 2 : 1;
   __shared__ double buf_re[4][fft_buf_len<N>()], buf_im[4][fft_buf_len<N>()];
   __shared__ float fr[NS][FB][N];   // windowed time-domain frames of this chunk (the reference's istft keeps them in
@@ -322,7 +329,7 @@ __global__ __launch_bounds__(256) void mask_istft_kernel(const float* __restrict
   float2 xv[FPL];
   float mav[FPL], mbv[FPL], xnyq, manyq, mbnyq;
   [[maybe_unused]] float2 pav[FPL], pbv[FPL];          // PHASE: the two speakers' phase vectors of this lane's bins
-  [[maybe_unused]] float xnyq_im, panyq, pbnyq;        // PHASE: Im X[N/2] (for |X|) and the real parts of the Nyquist phases
+  [[maybe_unused]] float xnyq_im, panyq, pbnyq;        // PHASE: Im X[N/2] (for |X|; MAG too) and the real parts of the Nyquist phases
   auto fetch = [&](int round) {
     const int t = tfirst + round * 4 + wave, tt = t < Tb ? t : Tb - 1;
     const float* xs = stft_ri + ((long)b * T + tt) * F * 2;
@@ -353,6 +360,7 @@ __global__ __launch_bounds__(256) void mask_istft_kernel(const float* __restrict
       panyq = pa[N];
       if constexpr (PAIR) pbnyq = pb[N];
     }
+    if constexpr (MAG) xnyq_im = xs[N + 1];
   };
   fetch(0);                                            // (requested before the lane constants are built: their table loads and these are one round trip)
   constexpr bool kLaneConst = (N / 4 == 64) && !FftPlan<N>::kOdd;
@@ -389,6 +397,13 @@ __global__ __launch_bounds__(256) void mask_istft_kernel(const float* __restrict
         ai = dc ? 0.0 : ma * (double)pav[k].y;
         br = PAIR ? mb * (double)pbv[k].x : 0.0;
         bi = (PAIR && !dc) ? mb * (double)pbv[k].y : 0.0;
+      } else if constexpr (MAG) {    // S = m X / |X|
+        const float h = hypotf(xv[k].x, xv[k].y);
+        const float ux = h > 0.0f ? xv[k].x / h : 1.0f, uy = h > 0.0f ? xv[k].y / h : 0.0f;
+        const double m = active ? (double)mav[k] : 0.0;
+        ar = m * (double)ux;
+        ai = dc ? 0.0 : m * (double)uy;
+        br = 0.0; bi = 0.0;
       } else {
       const double xr = active ? (double)xv[k].x : 0.0, xi = (active && !dc) ? (double)xv[k].y : 0.0;
       const double ma = (double)mav[k], mb = (double)mbv[k];
@@ -406,6 +421,10 @@ __global__ __launch_bounds__(256) void mask_istft_kernel(const float* __restrict
         const double mag = active ? (double)hypotf(xnyq, xnyq_im) : 0.0;
         re[jnyq] = mag * (double)manyq * (double)panyq;
         im[jnyq] = PAIR ? mag * (double)mbnyq * (double)pbnyq : 0.0;
+      } else if constexpr (MAG) {
+        const float h = hypotf(xnyq, xnyq_im);
+        re[jnyq] = active ? (double)manyq * (double)(h > 0.0f ? xnyq / h : 1.0f) : 0.0;
+        im[jnyq] = 0.0;
       } else {
       const double xr = active ? (double)xnyq : 0.0;
       re[jnyq] = xr * (double)manyq;

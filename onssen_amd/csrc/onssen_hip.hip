@@ -22,6 +22,8 @@
 //                       sdr_* (batch SI-SDR with best permutation, fp64 sums)
 //   loss_sisnr.inc      sisnr_* (Conv-TasNet's SI-SNR permutation-invariant training loss: value, assignment, gradient; fp64 moments)
 //   loss_phase.inc      loss_phase_* (phase_net's training loss: mask term and cosine phase term in one pass, assignment, gradient)
+//   enhance.inc         labels_enhance_kernel (|X|, |S|, cos of the phase difference in one pass), loss_enhance_* (the MSA / PSA
+//                       enhancement losses: value and gradient); the reconstruction is mask_istft_kernel's magnitude mode (fft.inc)
 //   pack.inc            one-off weight re-layout (gate permutation, MFMA fragment order, BatchNorm fold); training glue: dropout,
 //                       row-wise L2 normalisation and train-mode BatchNorm with their backward passes
 #include <hip/hip_runtime.h>
@@ -136,6 +138,7 @@ static unsigned& xcd_spin_limit() {
 #include "tasnet_run.inc" // Conv-TasNet: the one launch sequence behind the eval, ragged, training and stream entries
 #include "loss_sisnr.inc" // Conv-TasNet training: the SI-SNR permutation-invariant loss and its gradient
 #include "loss_phase.inc" // phase_net training: mask term + phase term of loss_phase in one pass, and their gradient
+#include "enhance.inc"    // speech enhancement: training labels, the MSA / PSA losses and their gradient
 
 // Co-tenant probe (tools/cotenant_probe.py): `workgroups` workgroups of `threads` threads that do nothing but hold their
 // CU for `ticks` ticks of the 100 MHz wall clock -- a stand-in for RCCL's channel kernels next to the persistent recurrences.
@@ -1218,7 +1221,7 @@ int onssen_debug_fft_stamps(long long* host_out, int n) {      // profile builds
 static int mask_istft_impl(const float* stft_ri, const float* mask, int64_t m_sb, int64_t m_sc, int64_t m_st,
                            int64_t m_sf, int B, int C, int T, int n_fft, int hop, int length, float* out,
                            void* stream, const int32_t* frames, const int32_t* lengths, const float* phase = nullptr,
-                           int64_t p_sc = 0) {
+                           int64_t p_sc = 0, bool magnitude = false) {
   if (!stft_ri || !out || B <= 0 || C <= 0 || T <= 0 || hop <= 0 || length <= 0 || hop > n_fft) return ONSSEN_E_ARG;
   if (reinterpret_cast<uintptr_t>(stft_ri) & 7u) return ONSSEN_E_ALIGN;               // (re, im) pairs are read as one 8-byte word
   if (phase && ((reinterpret_cast<uintptr_t>(phase) & 7u) || (p_sc & 1))) return ONSSEN_E_ALIGN;   // so are the phase vectors
@@ -1228,7 +1231,7 @@ static int mask_istft_impl(const float* stft_ri, const float* mask, int64_t m_sb
   // two; FB frames of both speakers then share the LDS, so the longer transforms keep fewer frames per workgroup
   const bool hop_aligned = (n_fft % hop) == 0 && ((n_fft / 2) % hop) == 0;
   const int halo = ceil_div(n_fft, hop) - 1 + (hop_aligned ? 0 : 1);
-  bool pair = C >= 2 && n_fft <= 512;
+  bool pair = C >= 2 && n_fft <= 512 && !magnitude;      // (the magnitude form has one estimate per input: unpaired only)
   int FB = pair ? (n_fft <= 256 ? 16 : 8) : (n_fft <= 512 ? 16 : 8);
   if (pair && FB - halo <= 0) {      // very small hops: the unpaired form keeps more frames per workgroup
     pair = false;
@@ -1254,16 +1257,26 @@ static int mask_istft_impl(const float* stft_ri, const float* mask, int64_t m_sb
   ONSSEN_CLEAR_ERROR();
   const dim3 grid((unsigned)ceil_div(length, FR * hop), (unsigned)(pair ? ceil_div(C, 2) : C), (unsigned)B), block(256);
   hipStream_t st = (hipStream_t)stream;
-  // (phase: the phase-aware operand of onssen_phase_istft_f32 -- the same geometry, its own instantiation of every form)
+  // (phase: the phase-aware operand of onssen_phase_istft_f32 -- the same geometry, its own instantiation of every form;
+  // magnitude: the operand of onssen_mag_istft_f32, the unpaired forms only)
 #define ONSSEN_ISTFT(N_, FB_, PAIR_)                                                                                    \
   do {                                                                                                                  \
     if (phase)                                                                                                          \
-      hipLaunchKernelGGL((mask_istft_kernel<N_, FB_, PAIR_, true>), grid, block, 0, st, stft_ri, mask, (long)m_sb,      \
+      hipLaunchKernelGGL((mask_istft_kernel<N_, FB_, PAIR_, ISTFT_PHASE>), grid, block, 0, st, stft_ri, mask, (long)m_sb, \
                          (long)m_sc, (long)m_st, (long)m_sf, C, T, hop, length, FR, out, frames, lengths, phase, (long)p_sc); \
     else                                                                                                                \
-      hipLaunchKernelGGL((mask_istft_kernel<N_, FB_, PAIR_, false>), grid, block, 0, st, stft_ri, mask, (long)m_sb,     \
+      hipLaunchKernelGGL((mask_istft_kernel<N_, FB_, PAIR_, ISTFT_MASK>), grid, block, 0, st, stft_ri, mask, (long)m_sb, \
                          (long)m_sc, (long)m_st, (long)m_sf, C, T, hop, length, FR, out, frames, lengths, phase, (long)p_sc); \
   } while (0)
+#define ONSSEN_ISTFT_MAG(N_, FB_)                                                                                       \
+  hipLaunchKernelGGL((mask_istft_kernel<N_, FB_, false, ISTFT_MAG>), grid, block, 0, st, stft_ri, mask, (long)m_sb,     \
+                     (long)m_sc, (long)m_st, (long)m_sf, C, T, hop, length, FR, out, frames, lengths, phase, (long)p_sc)
+  if (magnitude) {
+    if (n_fft == 256) ONSSEN_ISTFT_MAG(256, 16);
+    else if (n_fft == 512) ONSSEN_ISTFT_MAG(512, 16);
+    else if (n_fft == 1024) ONSSEN_ISTFT_MAG(1024, 8);
+    else return ONSSEN_E_ARG;
+  } else
   if (n_fft == 256) {
     if (!pair) ONSSEN_ISTFT(256, 16, false);
     else if (FB == 8) ONSSEN_ISTFT(256, 8, true);
@@ -1274,6 +1287,7 @@ static int mask_istft_impl(const float* stft_ri, const float* mask, int64_t m_sb
   else if (n_fft == 1024) ONSSEN_ISTFT(1024, 8, false);
   else
     return ONSSEN_E_ARG;
+#undef ONSSEN_ISTFT_MAG
   ONSSEN_LAUNCH_CHECK();
   return ONSSEN_OK;
 }
@@ -1297,6 +1311,21 @@ int onssen_phase_istft_f32(const float* stft_ri, const float* mask, int64_t m_sb
   if (!phase) return ONSSEN_E_ARG;
   return mask_istft_impl(stft_ri, mask, m_sb, m_sc, m_st, m_sf, B, C, T, n_fft, hop, length, out, stream, nullptr, nullptr, phase,
                          p_sc);
+}
+
+int onssen_mag_istft_f32(const float* stft_ri, const float* mag, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf, int B,
+                         int C, int T, int n_fft, int hop, int length, float* out, void* stream) {
+  if (!mag) return ONSSEN_E_ARG;
+  return mask_istft_impl(stft_ri, mag, m_sb, m_sc, m_st, m_sf, B, C, T, n_fft, hop, length, out, stream, nullptr, nullptr, nullptr, 0,
+                         true);
+}
+
+int onssen_mag_istft_ragged_f32(const float* stft_ri, const float* mag, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf,
+                                int B, int C, int T, const int32_t* frames, int n_fft, int hop, int length, const int32_t* lengths,
+                                float* out, void* stream) {
+  if (!mag || !frames || !lengths) return ONSSEN_E_ARG;
+  return mask_istft_impl(stft_ri, mag, m_sb, m_sc, m_st, m_sf, B, C, T, n_fft, hop, length, out, stream, frames, lengths, nullptr, 0,
+                         true);
 }
 
 }  // extern "C"

@@ -6,6 +6,9 @@ carry the author's corpus path).  A ``data_path`` that is given but holds no fil
 like the reference's empty dataset would fail -- numbers must never come from synthetic mixtures by accident.  Either way the
 features and labels are computed on the GPU and the yield contract is the reference's.
 
+``daps_enhance_dataloader`` (onssen/data/daps_enhance.py:30-35; data/daps_enhance.py here) follows the same rule with its list file
+``<data_path>/<partition>``.
+
 ``feature_utils`` carries the reference's helper names (``get_stft``, ``get_log_magnitude``, ``get_phase``, ``get_cos_difference``,
 ``get_one_hot``: onssen/data/feature_utils.py:5-21,49-95), NumPy in / NumPy out over the same device kernels."""
 import glob
@@ -14,6 +17,7 @@ import os
 from .. import options
 from . import feature_utils
 from .feature_utils import get_cos_difference, get_log_magnitude, get_one_hot, get_phase, get_stft
+from .daps_enhance import DapsEnhanceFiles, SyntheticDapsEnhance, daps_enhance_dataloader
 from .synthetic_wsj0_2mix import SyntheticVoicePairs, SyntheticWsj02mix
 from .wsj0_2mix import Wsj02mixFiles, read_wav, write_wav
 
@@ -32,5 +36,5 @@ def wsj0_2mix_dataloader(model_name, feature_options, partition, device=None):
                             f"{partition!r}); pass data_path='' / 'synthetic' or set ONSSEN_SYNTHETIC_DATA=1 for the synthetic corpus")
 
 
-__all__ = ["wsj0_2mix_dataloader", "feature_utils", "get_stft", "get_log_magnitude", "get_phase", "get_cos_difference", "get_one_hot",
+__all__ = ["wsj0_2mix_dataloader", "daps_enhance_dataloader", "DapsEnhanceFiles", "SyntheticDapsEnhance", "feature_utils", "get_stft", "get_log_magnitude", "get_phase", "get_cos_difference", "get_one_hot",
            "SyntheticVoicePairs", "SyntheticWsj02mix", "Wsj02mixFiles", "read_wav", "write_wav"]

@@ -328,6 +328,24 @@ class tester_phase(tester):
         return phase_istft(ri, masks, [phase_A, phase_B], self.hop_size, sig_ref.shape[-1]), sig_ref.float()
 
 
+class tester_enhance(tester):
+    """Speech enhancement (egs/daps; upstream's run.py ends in the bare ``tester``, whose ``get_est_sig`` is abstract): the
+    evaluation loader yields ``[feature_noisy (B,T,F), mag_noisy (B,T,F)]``, ``[stft_r (B,T,F), stft_i (B,T,F), sig_ref (B,1,n)]``
+    (``daps_enhance_dataloader`` with an evaluation partition); the network's output is the clean magnitude, and the estimate is
+    its inverse transform on the noisy signal's phase (``features.mag_istft``).  ``eval(batch=K)`` is the base class's ragged
+    path: ``mag_noisy`` is an input, so ``collate`` pads it along the frame axis like the features."""
+
+    def __init__(self, args, hop_size=64):
+        super().__init__(args)
+        self.hop_size = hop_size
+
+    def get_est_sig(self, input, label, output, frames=None, lengths=None):
+        from .features import mag_istft
+        clean_est, = output
+        ri, sig_ref = _mix_ri(label)
+        return mag_istft(ri, clean_est, self.hop_size, sig_ref.shape[-1], frames=frames, lengths=lengths), sig_ref.float()
+
+
 class tester_tasnet(tester):
     """egs/wsj0-2mix/tasnet/evaluate.py:11-29: the loader yields ``[mix (1, S')]``, ``[sig_ref (1, C, S')]`` per utterance and
     ConvTasNet's outputs are the estimates, cut to the reference's length.  ``eval()`` returns the mean SI-SDR.  ``batch=1``

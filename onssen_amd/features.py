@@ -141,3 +141,60 @@ def training_labels(stft_mix, stft_s1, stft_s2, feature_mix, db_threshold=40.0, 
                      float(db_threshold), umax.data_ptr(), one_hot.data_ptr(), mm.data_ptr(), m1.data_ptr(),
                      m2.data_ptr(), c1.data_ptr() if with_cos else None, c2.data_ptr() if with_cos else None, _stream())
     return (one_hot, mm, m1, m2, c1, c2) if with_cos else (one_hot, mm, m1, m2)
+
+
+def mag_istft(stft_ri, mags, hop_size=64, length=None, frames=None, lengths=None):
+    """stft_ri (B,T,F,2); mags (B,T,F,C) (any strides), or (B,T,F) for one channel -> (B, C, length) float32:
+    istft(mags_c * exp(i angle(stft))) per channel -- an estimated MAGNITUDE put back on the mixture's phase, the
+    reconstruction of the enhancement recipe (the ``enhance`` network returns a clean magnitude, not a mask).  A bin whose
+    spectrum is exactly 0 has phase 0, as np.angle gives it.
+
+    ``frames`` / ``lengths`` (B,): a RAGGED batch exactly as in ``mask_istft``."""
+    if not stft_ri.is_cuda:
+        raise RuntimeError("mag_istft: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
+    stft_ri = stft_ri.float().contiguous()
+    B, T, F, _ = stft_ri.shape
+    n_fft = 2 * (F - 1)
+    if length is None:
+        length = hop_size * (T - 1)
+    if (frames is None) != (lengths is None):
+        raise ValueError("mag_istft: a ragged batch needs both frames= and lengths=")
+    rag = {}
+    if frames is not None:
+        frames = _lengths_i32(frames, B, T, stft_ri.device, "frames")
+        lengths = _lengths_i32(lengths, B, length, stft_ri.device, "lengths")
+        rag = dict(frames=frames.data_ptr(), lengths=lengths.data_ptr())
+    mags = mags.float()
+    if mags.dim() == 3:
+        mags = mags.unsqueeze(-1)
+    if tuple(mags.shape[:3]) != (B, T, F):
+        raise ValueError(f"mag_istft: expected magnitudes of shape {(B, T, F)} (+ channels), got {tuple(mags.shape)}")
+    C = mags.shape[3]
+    out = torch.empty(B, C, length, device=stft_ri.device, dtype=torch.float32)
+    get_lib().mag_istft(stft_ri.data_ptr(), mags.data_ptr(), mags.stride(0), mags.stride(3), mags.stride(1), mags.stride(2),
+                        B, C, T, n_fft, hop_size, length, out.data_ptr(), _stream(), **rag)
+    return out
+
+
+def enhance_labels(stft_noisy, stft_clean, with_cos=True):
+    """Label-side features of the enhancement recipe on the GPU, one pass (onssen/data/daps_enhance.py:104-106: np.abs, np.abs,
+    get_cos_difference): (..., 2) float32 spectra of the noisy and the clean signal, as ``stft_logmag`` returns them ->
+    (mag_noisy, mag_clean, cos_diff), each of the spectra's shape without the last axis; ``with_cos=False`` leaves cos_diff out
+    (None): evaluation needs the magnitudes only.  ``stft_clean=None`` (separation has no clean signal): (mag_noisy, None, None)."""
+    if not stft_noisy.is_cuda:
+        raise RuntimeError("enhance_labels: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
+    if stft_noisy.shape[-1] != 2 or (stft_clean is not None and stft_clean.shape != stft_noisy.shape):
+        raise ValueError(f"enhance_labels: expected two (..., 2) spectra of one shape, got {tuple(stft_noisy.shape)} and "
+                         f"{None if stft_clean is None else tuple(stft_clean.shape)}")
+    stft_noisy = stft_noisy.float().contiguous()
+    shape, dev = stft_noisy.shape[:-1], stft_noisy.device
+    mk = lambda: torch.empty(shape, device=dev, dtype=torch.float32)
+    mag_noisy = mk()
+    if stft_clean is None:
+        get_lib().labels_enhance(stft_noisy.data_ptr(), None, mag_noisy.numel(), mag_noisy.data_ptr(), None, None, _stream())
+        return mag_noisy, None, None
+    stft_clean = stft_clean.float().contiguous()
+    mag_clean, cos_diff = mk(), (mk() if with_cos else None)
+    get_lib().labels_enhance(stft_noisy.data_ptr(), stft_clean.data_ptr(), mag_noisy.numel(), mag_noisy.data_ptr(),
+                             mag_clean.data_ptr(), cos_diff.data_ptr() if with_cos else None, _stream())
+    return mag_noisy, mag_clean, cos_diff

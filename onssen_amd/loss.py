@@ -8,6 +8,8 @@ autograd needs it, the gradient from ``onssen_loss_dc_grad_f32`` (``dV = Z M`` f
 PyTorch form on the GPU.
 The phase network's loss (``loss_phase``): the same deep-clustering term, and the mask term and cosine phase term from
 ``onssen_loss_phase_f32`` / ``onssen_loss_phase_grad_f32`` (one pass over the eleven maps forward, one elementwise pass backward).
+The enhancement losses (``loss_mask_msa`` / ``loss_mask_psa``, onssen/loss/loss_mask.py): one estimate against one target, value from
+``onssen_loss_enhance_f32`` and gradient from ``onssen_loss_enhance_grad_f32`` (csrc/enhance.inc), routed like the chimera losses.
 Semantics follow onssen/loss/loss_dc.py:6-44 and loss_util.py:4-11 exactly,
 including their quirks: the affinity terms are Frobenius *norms* (not squared
 norms) and the final product ``(B,) * (B,1)`` broadcasts to a (B, B) tensor
@@ -256,6 +258,121 @@ def loss_chimera_psa(output, label):
         t2 = torch.min(mag_mix, torch.relu(mag_s2 * cos_s2))
         lm = _mask_term(mask_A, mask_B, mag_mix, t1, t2)
     return le * 0.975 + lm * 0.025
+
+
+# ----------------------------------------------------------------------------- enhancement losses
+last_enhance_path = None
+
+
+def _enhance_route(is_cuda, needs_grad):
+    """Which form an enhancement loss takes, as the chimera losses choose: "value" (a ROCm tensor and no gradient wanted: the
+    value kernel), "grad" (a gradient wanted and option ``loss`` = "1": the autograd node over the two kernels), else "aten"
+    (PyTorch ops; always on the CPU)."""
+    if not is_cuda:
+        return "aten"
+    if not needs_grad:
+        return "value"
+    return "grad" if options.get("loss") == "1" else "aten"
+
+
+def _enhance_launch(mode, est, mag_noisy, mag_clean, cos_diff, scale, want_total):
+    from .hip import get_lib
+    lib = get_lib()
+    B = est.shape[0]
+    TF = est[0].numel()
+    dev = est.device
+    per_utt = torch.empty(B, device=dev, dtype=torch.float32)
+    total = torch.empty((), device=dev, dtype=torch.float32) if want_total else None
+    ws = torch.empty(lib.loss_enhance_workspace_bytes(B), dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    lib.loss_enhance(mode, est.data_ptr(), ptr(mag_noisy), mag_clean.data_ptr(), ptr(cos_diff), B, TF, scale, per_utt.data_ptr(),
+                     ptr(total), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    return per_utt, total
+
+
+class _EnhanceLossHip(torch.autograd.Function):
+    """An enhancement loss with the estimate's gradient on the device (csrc/enhance.inc): ``onssen_loss_enhance_f32`` forward,
+    ``onssen_loss_enhance_grad_f32`` backward, one elementwise pass.  MSA returns the scalar ``scale * sum (est - clean)^2``, PSA
+    the per-utterance sums (B,); the labels carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, mode, scale, est, mag_noisy, mag_clean, cos_diff):
+        from . import _abi
+        msa = mode == _abi.ENHANCE_MSA
+        per_utt, total = _enhance_launch(mode, est, mag_noisy, mag_clean, cos_diff, scale, msa)
+        ctx.geom = (mode, scale)
+        ctx.save_for_backward(est, mag_clean, *([] if msa else [mag_noisy, cos_diff]))
+        return total if msa else per_utt
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from .hip import get_lib
+        mode, scale = ctx.geom
+        est, mag_clean, *rest = ctx.saved_tensors
+        mag_noisy, cos_diff = rest if rest else (None, None)
+        d = torch.empty_like(est)
+        g = g.float().contiguous()
+        ptr = lambda t: None if t is None else t.data_ptr()
+        get_lib().loss_enhance_grad(mode, est.data_ptr(), ptr(mag_noisy), mag_clean.data_ptr(), ptr(cos_diff), est.shape[0],
+                                    est[0].numel(), scale, g.data_ptr(), d.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        return None, None, d, None, None, None
+
+
+def _enhance_hip(mode, route, est, mag_noisy, mag_clean, cos_diff, scale):
+    from . import _abi
+    lab = lambda t: None if t is None else t.detach().float().contiguous()
+    mag_noisy, mag_clean, cos_diff = lab(mag_noisy), lab(mag_clean), lab(cos_diff)
+    shape = est.shape
+    x = est.float().contiguous()
+    if route == "grad":
+        return _EnhanceLossHip.apply(mode, scale, x, mag_noisy, mag_clean, cos_diff)
+    msa = mode == _abi.ENHANCE_MSA
+    per_utt, total = _enhance_launch(mode, x.detach(), mag_noisy, mag_clean, cos_diff, scale, msa)
+    return total if msa else per_utt
+
+
+def loss_mask_msa(output, label):
+    """onssen/loss/loss_mask.py:6-22, magnitude spectrum approximation for enhancement: ``MSELoss()(clean_est, mag_clean)``, a
+    scalar -- the mean over all B T F bins.  ``output`` = [clean_est (B,T,F)] (the ``enhance`` network returns the clean
+    magnitude itself, no mask is applied here), ``label`` = [mag_clean, cos_diff] as ``daps_enhance_dataloader`` yields them;
+    cos_diff is not used, as upstream.  This is the loss of the recipe (egs/daps/run.py).
+
+    On ROCm tensors the value comes from ``onssen_loss_enhance_f32`` when no gradient is wanted, value and gradient from the
+    autograd node over the enhancement loss kernels with option ``loss`` = "1"; otherwise, and always on the CPU, PyTorch ops.
+    ``last_enhance_path`` ("value" | "grad" | "aten") says which route the last call took."""
+    global last_enhance_path
+    from . import _abi
+    assert len(output) == 1, "There must be 1 tensor in the output"
+    assert len(label) == 2, "There must be 2 tensors in the label"
+    clean_est, = output
+    mag_clean, _cos_diff = label
+    route = last_enhance_path = _enhance_route(clean_est.is_cuda, not _no_grad_needed(clean_est))
+    if route == "aten" or clean_est.shape != mag_clean.shape or clean_est.dim() < 2:
+        last_enhance_path = "aten"
+        return torch.nn.functional.mse_loss(clean_est, mag_clean)
+    return _enhance_hip(_abi.ENHANCE_MSA, route, clean_est, None, mag_clean, None, 1.0 / clean_est.numel())
+
+
+def loss_mask_psa(output, label):
+    """onssen/loss/loss_mask.py:25-40, phase-sensitive spectrum approximation: per utterance
+    ``sum |mask * mag_noisy - min(mag_noisy, relu(mag_clean * cos_diff))|``, (B,).  ``output`` = [mask (B,T,F)], ``label`` =
+    [mag_noisy, mag_clean, cos_diff].  Restated as upstream has it -- which is NOT what the DAPS loader yields (its label is
+    [mag_clean, cos_diff], mag_noisy travels with the input) nor what ``enhance`` returns (a magnitude, not a mask): upstream's
+    recipe trains with ``loss_mask_msa``, and so does this one; a caller with a mask-valued model builds the label list itself.
+    Routes as ``loss_mask_msa``."""
+    global last_enhance_path
+    from . import _abi
+    assert len(output) == 1, "There must be 1 tensor in the output"
+    assert len(label) == 3, "There must be 3 tensors in the label"
+    mask, = output
+    mag_noisy, mag_clean, cos_diff = label
+    route = last_enhance_path = _enhance_route(mask.is_cuda, not _no_grad_needed(mask))
+    same = mask.shape == mag_noisy.shape == mag_clean.shape == cos_diff.shape
+    if route == "aten" or not same or mask.dim() < 2:
+        last_enhance_path = "aten"
+        return _l1(mask * mag_noisy - torch.min(mag_noisy, torch.relu(mag_clean * cos_diff)))
+    return _enhance_hip(_abi.ENHANCE_PSA, route, mask, mag_noisy, mag_clean, cos_diff, 1.0)
 
 
 # ----------------------------------------------------------------------------- phase network loss

@@ -5,7 +5,7 @@ from .. import options
 
 from ._train import batch_norm_rows
 from ._core import (PackedWeightsMixin, needs_graph, BLSTMParams, PackedBLSTM, PackedHead, _Workspaces, EPI_RELU, EPI_SIGMOID, _stream, _version_key,
-                    heads_take_image, require_device, run_blstm, run_head, use_hip_path)
+                    as_frames, heads_take_image, require_device, run_blstm, run_head, use_hip_path)
 from ..hip import get_lib
 
 
@@ -48,15 +48,23 @@ class enhance(PackedWeightsMixin, nn.Module):
             self._small = (key, ws[0], ws[1], ld)
         return self._small[1:]
 
-    def forward(self, input):
+    def forward(self, input, frames=None):
+        """``frames`` (extension; inference only): per-row frame counts of a ragged batch of whole utterances, as in
+        ``chimera.forward`` -- row b's estimate inside its own frames is bit for bit its batch-1 result (the recurrence's ragged
+        form; every GEMM here has one tile shape and one k-order whatever the row count, and rows do not mix); the rows after
+        them hold no meaning."""
         assert len(input) == 2, "There must be two tensors in the input for the enhance network"
         x, mag_noisy = input[0].float(), input[1].float()
         batch_size, frame, frequency = x.size()
         if not use_hip_path(self) or needs_graph(*input):
+            if frames is not None:
+                raise RuntimeError("enhance: frames=... (ragged batch) is an inference-path extension")
             return [self._autograd_forward(x, mag_noisy)]
         require_device(x, "enhance")
         lib = get_lib()
-        y = run_blstm(self._packed, self._ws, x, need_y=not heads_take_image(batch_size, self.hidden_dim))
+        if frames is not None:
+            frames = as_frames(frames, batch_size, frame, x.device)
+        y = run_blstm(self._packed, self._ws, x, frames=frames, need_y=not heads_take_image(batch_size, self.hidden_dim))
         mask = run_head(self._head, y, batch_size, frame, EPI_SIGMOID)                 # (B, T, F)
         w_pre, w_post, ld = self._small_weights()
         mag = mag_noisy.contiguous()

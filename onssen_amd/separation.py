@@ -49,6 +49,23 @@ def separate_phase(model, wav, window_size=256, hop_size=64):
     return out
 
 
+@recovering
+@torch.no_grad()
+def separate_enhance(model, wav, window_size=256, hop_size=64, lengths=None):
+    """Speech enhancement, waveform in -> (B, n) waveform out (egs/daps: ``enhance`` estimates the clean MAGNITUDE, which goes
+    back to a waveform on the noisy signal's phase): STFT -> |X| -> ``model([logmag, |X|])`` -> ``features.mag_istft``.  Nothing is
+    read back by the host, so a call can be captured in a hipGraph.  ``lengths`` (B,): a ragged batch of whole utterances padded
+    to n samples; every row inside its own length is bit for bit its batch-1 result, zeros after it (see separate_dc)."""
+    from .features import enhance_labels, mag_istft
+    lengths, frames = _ragged(wav, lengths, hop_size)
+    logmag, ri = stft_logmag(wav, window_size, hop_size, lengths=lengths)
+    mag = enhance_labels(ri, None)[0]
+    clean, = model([logmag, mag]) if frames is None else model([logmag, mag], frames=frames)
+    out = mag_istft(ri, clean, hop_size, wav.shape[-1], frames=frames, lengths=lengths)
+    _XcdStatus.flush()            # an aborted recurrence is caught HERE (and the call re-run, see `recovering`), not by the next call
+    return out[:, 0]
+
+
 @torch.no_grad()
 def separate_tasnet(model, waves):
     """Time-domain separation of whole utterances: ``waves`` a list of 1-D waveforms of any lengths (one device) -> a list of
