@@ -11,15 +11,15 @@ constexpr int SMEM = (BM * CLD > STAGE) ? BM * CLD : STAGE;
 }  // namespace lin
 
 struct LinearArgs {
-  const float* A;
-  long a_s0, a_s1;
-  const float* W;
-  const float* bias;
-  const float* resid;
-  float* C;
-  long c_s0, c_s1;
-  int R, M, N, K, ldw, group;
-  float eps;
+  const float* A = nullptr;
+  long a_s0 = 0, a_s1 = 0;
+  const float* W = nullptr;
+  const float* bias = nullptr;
+  const float* resid = nullptr;
+  float* C = nullptr;
+  long c_s0 = 0, c_s1 = 0;
+  int R = 1, M = 0, N = 0, K = 0, ldw = 0, group = 0;
+  float eps = 0.f;
 };
 
 __device__ __forceinline__ float f4c(const float4& v, int r) {
@@ -193,19 +193,19 @@ constexpr int smem_bytes(int bm) { return stage_bytes(bm) > EPI_BYTES ? stage_by
 }  // namespace lx3
 
 struct LinearX3Args {
-  const float* A;
-  long a_s0, a_s1;
-  const unsigned short* Whi;
-  const unsigned short* Wlo;
-  const float* bias;
-  const float* resid;
-  float* C;
-  long c_s0, c_s1;
-  int R, M, N, K, ldw, group;
-  float eps;
-  int c_vec;    // C rows 16-byte aligned and N % 4 == 0
-  int tile_group;  // N-tiles walked together (L2 blocking)
-  int ablate;   // profiling only (ONSSEN_X3_ABLATE): 1 no global loads, 2 no split/LDS store, 4 no MFMA, 8 no fragment reads
+  const float* A = nullptr;
+  long a_s0 = 0, a_s1 = 0;
+  const unsigned short* Whi = nullptr;
+  const unsigned short* Wlo = nullptr;
+  const float* bias = nullptr;
+  const float* resid = nullptr;
+  float* C = nullptr;
+  long c_s0 = 0, c_s1 = 0;
+  int R = 1, M = 0, N = 0, K = 0, ldw = 0, group = 0;
+  float eps = 0.f;
+  int c_vec = 0;    // C rows 16-byte aligned and N % 4 == 0
+  int tile_group = 4;  // N-tiles walked together (L2 blocking)
+  int ablate = 0;   // profiling only (ONSSEN_X3_ABLATE): 1 no global loads, 2 no split/LDS store, 4 no MFMA, 8 no fragment reads
 };
 
 __device__ __forceinline__ unsigned pack2(unsigned short a, unsigned short b) { return (unsigned)a | ((unsigned)b << 16); }
@@ -498,26 +498,26 @@ constexpr int STAGE = (BM + BN) * RS;        // 66,560 B per stage, two stages
 }  // namespace lxp
 
 struct LinearXpArgs {
-  const unsigned short* A;      // x3 image [M][KB][2][32]
-  const unsigned short* W;      // x3 image [N][KB][2][32]
-  const float* bias;
-  float* C;
-  long c_s0, c_s1;
-  int R, M, N, KB, group;
-  float eps;
-  int tile_group;
-  int c_vec;                    // C rows 16-byte aligned and N % 4 == 0
-  long a_bs, w_bs, c_bs;        // BATCH instantiation: element strides of A image / W image / C between the gridDim.z problems
-  float* C2;                    // BATCH: columns n >= n_split go to C2 (row addressing c2_s0 / c2_s1 / c2_bs, column n - n_split); null: none
+  const unsigned short* A = nullptr;      // x3 image [M][KB][2][32]
+  const unsigned short* W = nullptr;      // x3 image [N][KB][2][32]
+  const float* bias = nullptr;
+  float* C = nullptr;
+  long c_s0 = 0, c_s1 = 0;
+  int R = 1, M = 0, N = 0, KB = 0, group = 0;
+  float eps = 0.f;
+  int tile_group = 4;
+  int c_vec = 0;                // C rows 16-byte aligned and N % 4 == 0
+  long a_bs = 0, w_bs = 0, c_bs = 0;        // BATCH instantiation: element strides of A image / W image / C between the gridDim.z problems
+  float* C2 = nullptr;          // BATCH: columns n >= n_split go to C2 (row addressing c2_s0 / c2_s1 / c2_bs, column n - n_split); null: none
                                 // (linear_x3q_kernel, L2NORM with group > 2: [M][N / group] reciprocal clamped norms out; null: none)
-  long c2_s0, c2_s1, c2_bs;
-  int n_split;
-  int n_split_odd;              // BATCH with C2: != 0 -> the odd problems write columns < n_split_odd to C2 and the rest to C (outputs change places)
-  const float* resid;           // linear_x3q_kernel, L2NORM: added to A W^T + b before the normalisation; row m at resid + (m / R)*c_s0 +
-  int r_mod;                    // ((m % R) % r_mod)*c_s1 (the same residual for r_mod-periodic row blocks: the phase head's two speakers); null: none
-  const int* dest;              // linear_x3q_kernel, L2NORM_COMPACT: [R][dest_bs] target row of every (utterance b = m % R, bin t*F + f) inside
-  long dest_bs;                 // the utterance's compacted array C + b*c_s1 (rows of `group` floats), or -1: the group is not stored
-  int F;                        // ... bins per frame (t = m / R)
+  long c2_s0 = 0, c2_s1 = 0, c2_bs = 0;
+  int n_split = 0;
+  int n_split_odd = 0;          // BATCH with C2: != 0 -> the odd problems write columns < n_split_odd to C2 and the rest to C (outputs change places)
+  const float* resid = nullptr; // linear_x3q_kernel, L2NORM: added to A W^T + b before the normalisation; row m at resid + (m / R)*c_s0 +
+  int r_mod = 1;                // ((m % R) % r_mod)*c_s1 (the same residual for r_mod-periodic row blocks: the phase head's two speakers); null: none
+  const int* dest = nullptr;    // linear_x3q_kernel, L2NORM_COMPACT: [R][dest_bs] target row of every (utterance b = m % R, bin t*F + f) inside
+  long dest_bs = 0;             // the utterance's compacted array C + b*c_s1 (rows of `group` floats), or -1: the group is not stored
+  int F = 0;                    // ... bins per frame (t = m / R)
 };
 
 // profiling builds only (-DONSSEN_XP_ABLATE=bits; compile time, a run-time test per load would wreck the
@@ -808,16 +808,16 @@ struct XtSeg {
   int out_len;                  // columns of the segment that are stored (<= len: the rest is the image's zero padding)
 };
 struct LinearXtArgs {
-  const unsigned short* A;      // row-major x3 image of the [K][>= a_col0 + M] matrix whose columns are this GEMM's rows
-  long a_pitch;
-  int a_col0[2];                // per problem
-  XtSeg seg[2][2];              // per problem: the GEMM's columns [0, seg[z][0].len) and [seg[z][0].len, N)
-  const unsigned short* zero;   // 16 readable zero bytes
-  int M, N, K;                  // K = contraction length (image rows)
-  float* C[2][2];               // per problem, per segment: dense output, row m at C + (m / R) * s0 + (m % R) * s1, column n - segment start
-  long s0[2][2], s1[2][2];
-  int R;
-  int tile_group;
+  const unsigned short* A = nullptr;      // row-major x3 image of the [K][>= a_col0 + M] matrix whose columns are this GEMM's rows
+  long a_pitch = 0;
+  int a_col0[2] = {0, 0};       // per problem
+  XtSeg seg[2][2] = {};              // per problem: the GEMM's columns [0, seg[z][0].len) and [seg[z][0].len, N)
+  const unsigned short* zero = nullptr;   // 16 readable zero bytes
+  int M = 0, N = 0, K = 0;      // K = contraction length (image rows)
+  float* C[2][2] = {};          // per problem, per segment: dense output, row m at C + (m / R) * s0 + (m % R) * s1, column n - segment start
+  long s0[2][2] = {}, s1[2][2] = {};
+  int R = 1;
+  int tile_group = 4;
 };
 
 #ifndef ONSSEN_XT_ABLATE          // profiling builds only: 1 no global loads, 2 plain ds_read_b64 instead of the transposing read, 4 no LDS stores, 8 no MFMA

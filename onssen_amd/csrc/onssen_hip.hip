@@ -9,6 +9,7 @@
 //                       layout, 8 waves, register epilogues), linear_x3p_kernel (round-1 form: 256x160 tiles; batched weight gradients;
 //                       bias | sigmoid | grouped L2-norm), linear_x3_kernel / linear_kernel (fp32-A forms, exact-fp32 MFMA),
 //                       x3_image(_t)_kernel (fp32 -> split-bf16 operand images)
+//   gemm_run.inc        host code: the GEMMs' argument filler, tile chooser, dispatchers, environment switches and C ABI entries
 //   lstm.inc            lstm_xcd_kernel (K4, default: XCD-local persistent recurrence, ONE launch per layer, data-tagged h
 //                       exchange through the XCD's L2; split-bf16 / bf16 / exact-fp32 instantiations), lstm_step_kernel (one
 //                       launch per time step: H > 640 and the re-run of an aborted call)
@@ -93,6 +94,8 @@ __device__ __forceinline__ s16x4 lds_read_tr16(const unsigned short* p) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// grid of an element-wise kernel: one 256-thread workgroup per 256 elements, 8192 at the most (the kernels stride over the rest)
+static unsigned ew_blocks(long total) { const long nb = (total + 255) / 256; return (unsigned)(nb > 8192 ? 8192 : nb); }
 // Experiment / ablation switches exist only in builds made with -DONSSEN_DEBUG_KNOBS (tools/ab_variants.py): the product
 // library reads no environment variable for them and carries their defaults as constants.
 #ifdef ONSSEN_DEBUG_KNOBS
@@ -102,12 +105,6 @@ static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 #endif
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline bool aligned256(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 255u) == 0; }
-#ifndef ONSSEN_X3Q_SMALL_DEFAULT
-#define ONSSEN_X3Q_SMALL_DEFAULT 0   // onssen_linear_x3p, bias mode: KB (32-k blocks) up to which 128 x 128 tiles run (0 = never); ONSSEN_X3Q_SMALL overrides
-#endif
-#ifndef ONSSEN_X3R_DEFAULT
-#define ONSSEN_X3R_DEFAULT 0     // onssen_linear_x3p, bias mode: 1 = the 32x32x16-MFMA kernel (linear_x3r_kernel) unless ONSSEN_X3R=0 says otherwise
-#endif
 
 // Bounded waits of the persistent kernels: ~0.2 s of polling on the GPU by default.  A run-time setting of the library
 // (onssen_xcd_spin_limit), initialised from ONSSEN_XCD_SPIN_LIMIT: the host-side emulation -- where a 'workgroup' is a
@@ -121,6 +118,7 @@ static unsigned& xcd_spin_limit() {
 // ---- device code, one translation unit (the host-side emulation compiles exactly this file too)
 #include "pack.inc"
 #include "gemm.inc"
+#include "gemm_run.inc"    // GEMM host side: argument filler, tile chooser, dispatchers, environment switches and the C ABI entries over gemm.inc
 #include "labels_cluster.inc"
 #include "kmeans_k.inc"     // deep-clustering back end for 2 .. 4 speakers: its kernels and its C ABI entries
 #include "dc_run.inc"       // deep-clustering 2-means host side: one workspace layout, one Lloyd launcher, the C ABI entries over labels_cluster.inc
@@ -334,446 +332,9 @@ int onssen_head_pack_f32(const float* w, const float* b, int N, int H, int Hp, c
   return ONSSEN_OK;
 }
 
-int onssen_linear_f32(const float* A, int64_t a_s0, int64_t a_s1, int R, int M, int K, const float* W, int ldw,
-                      const float* bias, int N, int mode, int group, float eps, const float* resid, float* C,
-                      int64_t c_s0, int64_t c_s1, void* stream) {
-  if (!A || !W || !bias || !C || R <= 0 || M <= 0 || K <= 0 || N <= 0 || ldw < K) return ONSSEN_E_ARG;
-  if ((ldw % 4) != 0 || !aligned16(W)) return ONSSEN_E_ALIGN;
-  if (mode == ONSSEN_EPI_L2NORM) {
-    if (group <= 0 || (lin::BN % group) != 0 || (N % group) != 0) return ONSSEN_E_ARG;
-  } else if (resid && mode != ONSSEN_EPI_RELU) {
-    return ONSSEN_E_ARG;
-  }
-  ONSSEN_CLEAR_ERROR();
-  LinearArgs p;
-  p.A = A; p.a_s0 = (long)a_s0; p.a_s1 = (long)a_s1; p.W = W; p.bias = bias; p.resid = resid; p.C = C;
-  p.c_s0 = (long)c_s0; p.c_s1 = (long)c_s1; p.R = R; p.M = M; p.N = N; p.K = K; p.ldw = ldw; p.group = group;
-  p.eps = eps;
-  const bool a_vec = aligned16(A) && (a_s0 % 4) == 0 && (a_s1 % 4) == 0 && (K % 4) == 0;
-  const dim3 grid((unsigned)ceil_div(N, lin::BN), (unsigned)ceil_div(M, lin::BM)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define ONSSEN_LIN(VEC, MODE_) hipLaunchKernelGGL((linear_kernel<VEC, MODE_>), grid, block, 0, st, p)
-  if (mode == ONSSEN_EPI_BIAS) {
-    if (a_vec) ONSSEN_LIN(true, ONSSEN_EPI_BIAS); else ONSSEN_LIN(false, ONSSEN_EPI_BIAS);
-  } else if (mode == ONSSEN_EPI_L2NORM) {
-    if (a_vec) ONSSEN_LIN(true, ONSSEN_EPI_L2NORM); else ONSSEN_LIN(false, ONSSEN_EPI_L2NORM);
-  } else if (mode == ONSSEN_EPI_SIGMOID) {
-    if (a_vec) ONSSEN_LIN(true, ONSSEN_EPI_SIGMOID); else ONSSEN_LIN(false, ONSSEN_EPI_SIGMOID);
-  } else if (mode == ONSSEN_EPI_RELU) {
-    if (a_vec) ONSSEN_LIN(true, ONSSEN_EPI_RELU); else ONSSEN_LIN(false, ONSSEN_EPI_RELU);
-  } else {
-    return ONSSEN_E_ARG;
-  }
-#undef ONSSEN_LIN
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-int onssen_linear_pack_bf16x3(const float* w, int N, int K, int ld_in, int ld_out, uint16_t* planes, void* stream) {
-  if (!w || !planes || N <= 0 || K <= 0 || ld_in < K || ld_out < K || (ld_out % 32) != 0) return ONSSEN_E_ARG;
-  ONSSEN_CLEAR_ERROR();
-  const long n = (long)N * ld_out;
-  hipLaunchKernelGGL(pack_w_bf16x3_kernel, dim3((unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256)), dim3(256),
-                     0, (hipStream_t)stream, w, N, K, ld_in, ld_out, planes, planes + n);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-int onssen_linear_bf16x3(const float* A, int64_t a_s0, int64_t a_s1, int R, int M, int K, const uint16_t* w_planes,
-                         int ldw, const float* bias, int N, int mode, int group, float eps, const float* resid,
-                         float* C, int64_t c_s0, int64_t c_s1, void* stream) {
-  if (!A || !w_planes || !bias || !C || R <= 0 || M <= 0 || K <= 0 || N <= 0 || ldw < K) return ONSSEN_E_ARG;
-  if ((ldw % 32) != 0 || !aligned16(w_planes)) return ONSSEN_E_ALIGN;
-  if (mode == ONSSEN_EPI_L2NORM) {
-    if (group <= 0 || (lx3::BN % group) != 0 || (N % group) != 0) return ONSSEN_E_ARG;
-  } else if (resid) {
-    return ONSSEN_E_ARG;
-  }
-  ONSSEN_CLEAR_ERROR();
-  LinearX3Args p;
-  p.A = A; p.a_s0 = (long)a_s0; p.a_s1 = (long)a_s1; p.Whi = w_planes; p.Wlo = w_planes + (size_t)N * ldw;
-  p.bias = bias; p.resid = resid; p.C = C; p.c_s0 = (long)c_s0; p.c_s1 = (long)c_s1; p.R = R; p.M = M; p.N = N;
-  p.K = K; p.ldw = ldw; p.group = group; p.eps = eps;
-  static const int x3_ablate = ONSSEN_KNOB_INT("ONSSEN_X3_ABLATE", 0);
-  p.ablate = x3_ablate;
-  static const int x3_gn = ONSSEN_KNOB_INT("ONSSEN_X3_GN", 4);
-  p.tile_group = x3_gn < 1 ? 1 : x3_gn;
-  p.c_vec = aligned16(C) && (N % 4) == 0 && (c_s0 % 4) == 0 && (c_s1 % 4) == 0;
-  const bool a_vec = aligned16(A) && (a_s0 % 4) == 0 && (a_s1 % 4) == 0 && (K % 4) == 0;
-  // tile height: 256 rows x 1 workgroup per CU (default), or 128 rows x 2 co-resident (ONSSEN_X3_WM=2)
-  static const int wm_env = ONSSEN_KNOB_INT("ONSSEN_X3_WM", 0);
-  const int wmv = wm_env == 2 ? 2 : 4;   // measured: the 256-row tile re-reads W half as often and wins end to end
-  const dim3 grid((unsigned)ceil_div(N, lx3::BN), (unsigned)ceil_div(M, 64 * wmv)), block(128 * wmv);
-  hipStream_t st = (hipStream_t)stream;
-#define ONSSEN_LINX3(VEC, MODE_)                                                              \
-  do {                                                                                        \
-    if (wmv == 4) hipLaunchKernelGGL((linear_x3_kernel<VEC, MODE_, 4>), grid, block, 0, st, p); \
-    else hipLaunchKernelGGL((linear_x3_kernel<VEC, MODE_, 2>), grid, block, 0, st, p);          \
-  } while (0)
-  if (mode == ONSSEN_EPI_BIAS) {
-    if (a_vec) ONSSEN_LINX3(true, ONSSEN_EPI_BIAS); else ONSSEN_LINX3(false, ONSSEN_EPI_BIAS);
-  } else if (mode == ONSSEN_EPI_L2NORM) {
-    if (a_vec) ONSSEN_LINX3(true, ONSSEN_EPI_L2NORM); else ONSSEN_LINX3(false, ONSSEN_EPI_L2NORM);
-  } else if (mode == ONSSEN_EPI_SIGMOID) {
-    if (a_vec) ONSSEN_LINX3(true, ONSSEN_EPI_SIGMOID); else ONSSEN_LINX3(false, ONSSEN_EPI_SIGMOID);
-  } else {
-    return ONSSEN_E_ARG;
-  }
-#undef ONSSEN_LINX3
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-
-int onssen_x3_image_f32(const float* src, int64_t s0, int64_t s1, int R, int rows, int K, uint16_t* img, void* stream) {
-  if (!src || !img || R <= 0 || rows <= 0 || K <= 0) return ONSSEN_E_ARG;
-  if (!aligned16(img)) return ONSSEN_E_ALIGN;
-  ONSSEN_CLEAR_ERROR();
-  const int KB = ceil_div(K, 32);
-  const long n = (long)rows * KB * 4;
-  hipLaunchKernelGGL(x3_image_kernel, dim3((unsigned)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, src, (long)s0, (long)s1, R, rows, K, KB, img);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-int onssen_x3_image_t_f32(const float* src, int64_t ld, int M, int K, int k_shift, uint16_t* img, void* stream) {
-  if (!src || !img || M <= 0 || K <= 0 || ld < M) return ONSSEN_E_ARG;
-  if (!aligned16(img)) return ONSSEN_E_ALIGN;
-  ONSSEN_CLEAR_ERROR();
-  const int KB = ceil_div(K, 32);
-  hipLaunchKernelGGL(x3_image_t_kernel, dim3((unsigned)ceil_div(M, 64), (unsigned)KB), dim3(256), 0, (hipStream_t)stream, src,
-                     (long)ld, M, K, KB, k_shift, img);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-static int x3_image_both_impl(const float* src, int64_t ld, int M, int K, uint16_t* img_rows, uint16_t* img_t, float* colsum,
-                              void* stream) {
-  if (!src || !img_rows || !img_t || M <= 0 || K <= 0 || ld < M) return ONSSEN_E_ARG;
-  if (!aligned16(img_rows) || !aligned16(img_t)) return ONSSEN_E_ALIGN;
-  ONSSEN_CLEAR_ERROR();
-  const int KB = ceil_div(K, 32), MB = ceil_div(M, 32);
-  hipLaunchKernelGGL(x3_image_both_kernel, dim3((unsigned)ceil_div(M, 64), (unsigned)KB), dim3(256), 0, (hipStream_t)stream, src,
-                     (long)ld, M, K, KB, MB, img_rows, img_t, colsum);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-int onssen_x3_image_both_f32(const float* src, int64_t ld, int M, int K, uint16_t* img_rows, uint16_t* img_t, void* stream) {
-  return x3_image_both_impl(src, ld, M, K, img_rows, img_t, nullptr, stream);
-}
-
-int onssen_x3_image_both_colsum_f32(const float* src, int64_t ld, int M, int K, uint16_t* img_rows, uint16_t* img_t, float* colsum,
-                                    void* stream) {
-  if (!colsum) return ONSSEN_E_ARG;
-  return x3_image_both_impl(src, ld, M, K, img_rows, img_t, colsum, stream);
-}
-
-static int linear_x3p_batched_impl(const uint16_t* a_img, int64_t a_bs, int M, int K, const uint16_t* w_img, int64_t w_bs,
-                                   const float* bias, int N, int R, float* C, int64_t c_bs, int64_t c_s0, int64_t c_s1, int n_split,
-                                   float* C2, int64_t c2_bs, int64_t c2_s0, int64_t c2_s1, int batch, void* stream,
-                                   int n_split_odd = 0) {
-  if (!a_img || !w_img || !bias || !C || M <= 0 || K <= 0 || N <= 0 || R <= 0 || batch <= 0 || batch > 65535) return ONSSEN_E_ARG;
-  if (C2 && (n_split <= 0 || n_split >= N)) return ONSSEN_E_ARG;
-  if (n_split_odd && (!C2 || n_split_odd < 0 || n_split_odd >= N)) return ONSSEN_E_ARG;
-  if (!aligned16(a_img) || !aligned16(w_img) || (a_bs % 8) != 0 || (w_bs % 8) != 0) return ONSSEN_E_ALIGN;
-  const int KB = ceil_div(K, 32);
-  if ((long)lxp::BM * KB * 128 > 0x7fffffffL) return ONSSEN_E_ARG;
-  ONSSEN_CLEAR_ERROR();
-  LinearXpArgs p;
-  p.A = a_img; p.W = w_img; p.bias = bias; p.C = C; p.c_s0 = (long)c_s0; p.c_s1 = (long)c_s1; p.R = R; p.M = M; p.N = N;
-  p.KB = KB; p.group = 0; p.eps = 0.f; p.tile_group = 4;
-  p.c_vec = !C2 && aligned16(C) && (N % 4) == 0 && (c_s0 % 4) == 0 && (c_s1 % 4) == 0 && (c_bs % 4) == 0;
-  p.a_bs = (long)a_bs; p.w_bs = (long)w_bs; p.c_bs = (long)c_bs;
-  p.C2 = C2; p.c2_s0 = (long)c2_s0; p.c2_s1 = (long)c2_s1; p.c2_bs = (long)c2_bs; p.n_split = n_split; p.n_split_odd = n_split_odd;
-  p.resid = nullptr; p.r_mod = 1; p.dest = nullptr; p.dest_bs = 0; p.F = 0;
-  const dim3 grid((unsigned)ceil_div(N, lxp::BN), (unsigned)ceil_div(M, lxp::BM), (unsigned)batch);
-  hipLaunchKernelGGL((linear_x3p_kernel<ONSSEN_EPI_BIAS, 4, 3, true>), grid, dim3(512), 0, (hipStream_t)stream, p);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-int onssen_linear_x3p_batched(const uint16_t* a_img, int64_t a_bs, int M, int K, const uint16_t* w_img, int64_t w_bs,
-                              const float* bias, int N, float* C, int64_t c_bs, int64_t ldc, int batch, void* stream) {
-  if (ldc < N) return ONSSEN_E_ARG;
-  return linear_x3p_batched_impl(a_img, a_bs, M, K, w_img, w_bs, bias, N, 1, C, c_bs, ldc, 0, 0, nullptr, 0, 0, 0, batch, stream);
-}
-
-int onssen_linear_x3p_batched_split(const uint16_t* a_img, int64_t a_bs, int M, int K, const uint16_t* w_img, int64_t w_bs,
-                                    const float* bias, int N, int R, float* C, int64_t c_bs, int64_t c_s0, int64_t c_s1,
-                                    int n_split, float* C2, int64_t c2_bs, int64_t c2_s0, int64_t c2_s1, int batch, void* stream) {
-  if (!C2) return ONSSEN_E_ARG;
-  return linear_x3p_batched_impl(a_img, a_bs, M, K, w_img, w_bs, bias, N, R, C, c_bs, c_s0, c_s1, n_split, C2, c2_bs, c2_s0, c2_s1,
-                                 batch, stream);
-}
-
-int onssen_linear_x3p_batched_split_alt(const uint16_t* a_img, int64_t a_bs, int M, int K, const uint16_t* w_img, int64_t w_bs,
-                                        const float* bias, int N, int R, float* C, int64_t c_bs, int64_t c_s0, int64_t c_s1,
-                                        int n_split, float* C2, int64_t c2_bs, int64_t c2_s0, int64_t c2_s1, int n_split_odd,
-                                        int batch, void* stream) {
-  if (!C2 || n_split_odd <= 0) return ONSSEN_E_ARG;
-  return linear_x3p_batched_impl(a_img, a_bs, M, K, w_img, w_bs, bias, N, R, C, c_bs, c_s0, c_s1, n_split, C2, c2_bs, c2_s0, c2_s1,
-                                 batch, stream, n_split_odd);
-}
-
-// dW of one bidirectional LSTM layer from ROW-MAJOR images (linear_x3t_kernel): dp_img [K = T*B][2*NP / 32][2][32] (dL/d pre-activation),
-// y_img [K][2*Hp / 32][2][32] (the layer's output), x_img [K][ceil(Kx / 32)][2][32] (its input); per direction
-//   dW_hh[d] (R-mapped rows, Hp columns) = dP_d^T h_prev_d,   dW_ih[d] (Kx columns) = dP_d^T x
-// with h_prev = y rows shifted by -B (forward) / +B (reverse).
-int onssen_lstm_wgrad_images_f32(const uint16_t* dp_img, const uint16_t* y_img, const uint16_t* x_img, int K, int B, int NP, int Hp,
-                                 int Kx, const float* zero16, int R, float* dW_ih, int64_t ih_bs, int64_t ih_s0, int64_t ih_s1,
-                                 float* dW_hh, int64_t hh_bs, int64_t hh_s0, int64_t hh_s1, void* stream) {
-  if (!dp_img || !y_img || !x_img || !zero16 || !dW_ih || !dW_hh || K <= 0 || B <= 0 || R <= 0 || NP <= 0 || Hp <= 0 || Kx <= 0 ||
-      (NP % 32) != 0 || (Hp % 8) != 0 || (long)K * ((2 * NP) / 32) * 128 > 0x7fffffffL)
-    return ONSSEN_E_ARG;
-  const int Kx8 = (Kx + 7) & ~7;          // x is read in 8-column pieces: up to 7 columns of its image's zero padding, never stored
-  if (!aligned16(dp_img) || !aligned16(y_img) || !aligned16(x_img) || !aligned16(zero16)) return ONSSEN_E_ALIGN;
-  ONSSEN_CLEAR_ERROR();
-  LinearXtArgs p;
-  p.A = dp_img; p.a_pitch = (long)(2 * NP / 32) * 128; p.a_col0[0] = 0; p.a_col0[1] = NP;
-  const long y_pitch = (long)ceil_div(2 * Hp, 32) * 128, x_pitch = (long)ceil_div(Kx, 32) * 128;
-  // forward direction: [h_prev (y columns [0, Hp), rows k - B) | x];  reverse: [x | h_prev (y columns [Hp, 2 Hp), rows k + B)]
-  p.seg[0][0] = XtSeg{y_img, y_pitch, 0, Hp, -B, Hp};   p.seg[0][1] = XtSeg{x_img, x_pitch, 0, Kx8, 0, Kx};
-  p.seg[1][0] = XtSeg{x_img, x_pitch, 0, Kx8, 0, Kx};   p.seg[1][1] = XtSeg{y_img, y_pitch, Hp, Hp, B, Hp};
-  p.zero = (const unsigned short*)zero16;
-  p.M = NP; p.N = Hp + Kx8; p.K = K; p.R = R; p.tile_group = 4;
-  p.C[0][0] = dW_hh;           p.s0[0][0] = hh_s0; p.s1[0][0] = hh_s1;
-  p.C[0][1] = dW_ih;           p.s0[0][1] = ih_s0; p.s1[0][1] = ih_s1;
-  p.C[1][0] = dW_ih + ih_bs;   p.s0[1][0] = ih_s0; p.s1[1][0] = ih_s1;
-  p.C[1][1] = dW_hh + hh_bs;   p.s0[1][1] = hh_s0; p.s1[1][1] = hh_s1;
-  const dim3 grid((unsigned)ceil_div(p.N, 160), (unsigned)ceil_div(p.M, 256), 2);
-  hipLaunchKernelGGL((linear_x3t_kernel<3>), grid, dim3(512), 0, (hipStream_t)stream, p);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-// C [M][N] (row m at C + m*ldc) = A^T W for row-major x3 images A [K][ceil(M/32)][2][32] and W [K][ceil(N/32)][2][32] (columns past
-// M / N: the images' zero padding): a weight gradient dW = dy^T x from the images of dy and x as they were made for the forward /
-// input-gradient GEMMs (linear_x3t_kernel, one problem, one segment).
-int onssen_linear_x3t(const uint16_t* a_img, const uint16_t* w_img, int K, int M, int N, const float* zero16, float* C, int64_t ldc,
-                      void* stream) {
-  if (!a_img || !w_img || !zero16 || !C || K <= 0 || M <= 0 || N <= 0 || ldc < N || (long)K * ceil_div(M, 32) * 128 > 0x7fffffffL)
-    return ONSSEN_E_ARG;
-  if (!aligned16(a_img) || !aligned16(w_img) || !aligned16(zero16)) return ONSSEN_E_ALIGN;
-  ONSSEN_CLEAR_ERROR();
-  LinearXtArgs p;
-  p.A = a_img; p.a_pitch = (long)ceil_div(M, 32) * 128; p.a_col0[0] = p.a_col0[1] = 0;
-  const long w_pitch = (long)ceil_div(N, 32) * 128;
-  const int N8 = (N + 7) & ~7;
-  for (int zz = 0; zz < 2; ++zz) {
-    p.seg[zz][0] = XtSeg{w_img, w_pitch, 0, N8, 0, N};
-    p.seg[zz][1] = XtSeg{w_img, w_pitch, 0, 0, 0, 0};
-    p.C[zz][0] = p.C[zz][1] = C;
-    p.s0[zz][0] = p.s0[zz][1] = ldc; p.s1[zz][0] = p.s1[zz][1] = 0;
-  }
-  p.zero = (const unsigned short*)zero16;
-  p.M = M; p.N = N8; p.K = K; p.R = 1; p.tile_group = 4;
-  const dim3 grid((unsigned)ceil_div(p.N, 160), (unsigned)ceil_div(p.M, 256), 1);
-  hipLaunchKernelGGL((linear_x3t_kernel<3>), grid, dim3(512), 0, (hipStream_t)stream, p);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-static int linear_x3p_impl(const uint16_t* a_img, int M, int K, const uint16_t* w_img, const float* bias, int N, int mode,
-                           int group, float eps, const float* resid, int resid_mod, float* C, int R, int64_t c_s0,
-                           int64_t c_s1, void* stream, float* inv_norm = nullptr) {
-  if (!a_img || !w_img || !bias || !C || R <= 0 || M <= 0 || K <= 0 || N <= 0) return ONSSEN_E_ARG;
-  if (!aligned16(a_img) || !aligned16(w_img)) return ONSSEN_E_ALIGN;
-  const int KB = ceil_div(K, 32);
-  if ((long)lxp::BM * KB * 128 > 0x7fffffffL) return ONSSEN_E_ARG;
-  const bool bf16_only = (mode & ONSSEN_EPI_BF16) != 0;   // plain bf16 products: hi halves only
-  mode &= ~ONSSEN_EPI_BF16;
-  // pairs (group 2) and the residual exist in the 256/128 x 320 kernel only (onssen_linear_x3p_resid)
-  const bool pairs = mode == ONSSEN_EPI_L2NORM && group == 2;
-  if (mode == ONSSEN_EPI_L2NORM) {
-    if (!pairs && (group <= 0 || (group % 4) != 0 || (80 % group) != 0 || 80 / group > 4)) return ONSSEN_E_ARG;
-    if ((N % group) != 0) return ONSSEN_E_ARG;
-  } else if (mode != ONSSEN_EPI_BIAS && mode != ONSSEN_EPI_SIGMOID) {
-    return ONSSEN_E_ARG;
-  }
-  if (resid && (mode != ONSSEN_EPI_L2NORM || resid_mod <= 0)) return ONSSEN_E_ARG;
-  if (inv_norm && (mode != ONSSEN_EPI_L2NORM || pairs)) return ONSSEN_E_ARG;
-  ONSSEN_CLEAR_ERROR();
-  LinearXpArgs p;
-  p.A = a_img; p.W = w_img; p.bias = bias; p.C = C; p.c_s0 = (long)c_s0; p.c_s1 = (long)c_s1; p.R = R; p.M = M; p.N = N;
-  p.KB = KB; p.group = group; p.eps = eps; p.resid = resid; p.r_mod = resid ? resid_mod : 1;
-  p.dest = nullptr; p.dest_bs = 0; p.F = 0;
-  p.a_bs = p.w_bs = p.c_bs = 0;
-  p.C2 = inv_norm; p.c2_s0 = p.c2_s1 = p.c2_bs = 0; p.n_split = 0; p.n_split_odd = 0;
-  static const int x3_gn = ONSSEN_KNOB_INT("ONSSEN_X3_GN", 4);
-  p.tile_group = x3_gn < 1 ? 1 : x3_gn;
-  p.c_vec = aligned16(C) && (N % 4) == 0 && (c_s0 % 4) == 0 && (c_s1 % 4) == 0;
-  hipStream_t st = (hipStream_t)stream;
-  // tile shape (linear_x3q_kernel, LDS-DMA staging): 256 or 128 rows x 320 or 256 columns, unless ONSSEN_X3Q=0 selects the
-  // round-1 kernel (256 x 160).  One workgroup per CU: the shape with the smallest (rounds of 256 workgroups) x (tile area)
-  // wins, half-height tiles charged 15 % for their lower MFMA : fragment-read ratio; the L2NORM epilogue needs whole feature
-  // groups per wave (80 columns) and stays at 320 columns.  ONSSEN_X3Q=320 / 256 forces the width, ONSSEN_X3Q_BM=256 / 128 the height.
-  const char* env_q = getenv("ONSSEN_X3Q");   // read per call: the tests switch it
-  const char* env_bm = getenv("ONSSEN_X3Q_BM");
-  const int use_q = (pairs || resid || inv_norm) ? 1 : env_q ? atoi(env_q) : 1, force_bm = env_bm ? atoi(env_bm) : 0;
-  if ((pairs || resid || inv_norm) && (long)lxq::BM_MAX * KB * 128 > 0x7fffffffL) return ONSSEN_E_ARG;
-  if (use_q && (long)lxq::BM_MAX * KB * 128 <= 0x7fffffffL) {
-    int bm = 256, bn = 320;
-    double best = 1e30;
-    for (int cbm = 256; cbm >= 128; cbm -= 128)
-      for (int cbn = 320; cbn >= 256; cbn -= 64) {
-        if (cbn == 256 && (mode == ONSSEN_EPI_L2NORM || use_q == 320)) continue;
-        if (cbn == 320 && use_q == 256 && mode != ONSSEN_EPI_L2NORM) continue;
-        if (force_bm && cbm != force_bm) continue;
-        const double cost = (double)ceil_div((long)ceil_div(M, cbm) * ceil_div(N, cbn), 256) * cbm * cbn * (cbm == 128 ? 1.15 : 1.0);
-        if (cost < best) { best = cost; bm = cbm; bn = cbn; }
-      }
-    const dim3 gridq((unsigned)ceil_div(N, bn), (unsigned)ceil_div(M, bm));
-#define ONSSEN_XQ2(MODE_, T_)                                                                                            \
-  do {                                                                                                                   \
-    if (bm == 256 && bn == 320) hipLaunchKernelGGL((linear_x3q_kernel<MODE_, T_, false, 320, 256>), gridq, dim3(512), 0, st, p);      \
-    else if (bm == 256) hipLaunchKernelGGL((linear_x3q_kernel<MODE_, T_, false, 256, 256>), gridq, dim3(512), 0, st, p); \
-    else if (bn == 320) hipLaunchKernelGGL((linear_x3q_kernel<MODE_, T_, false, 320, 128>), gridq, dim3(512), 0, st, p); \
-    else hipLaunchKernelGGL((linear_x3q_kernel<MODE_, T_, false, 256, 128>), gridq, dim3(512), 0, st, p);                \
-  } while (0)
-#define ONSSEN_XQ(MODE_)                                     \
-  do {                                                       \
-    if (bf16_only) ONSSEN_XQ2(MODE_, 1); else ONSSEN_XQ2(MODE_, 3); \
-  } while (0)
-    // the bias mode (the projections): v_mfma_f32_32x32x16_bf16 tiles (linear_x3r_kernel, round 6c) unless ONSSEN_X3R=0 -- every tile
-    // shape, so that a row's bits do not depend on the shape its batch selects
-    const char* env_r = getenv("ONSSEN_X3R");
-    const bool use_r = mode == ONSSEN_EPI_BIAS && (env_r ? atoi(env_r) != 0 : ONSSEN_X3R_DEFAULT != 0);
-    // short K (the first layer's projection: 5 k-steps, then 245 MB of C): 128 x 128 tiles, 64 KB of LDS -- two workgroups per CU, one's
-    // stores under the other's k-loop (round 6c experiment, ONSSEN_X3Q_SMALL = the largest KB that takes it; same bits as every x3q tile)
-    const char* env_s = getenv("ONSSEN_X3Q_SMALL");
-    const int small_kb = env_s ? atoi(env_s) : ONSSEN_X3Q_SMALL_DEFAULT;
-    if (mode == ONSSEN_EPI_BIAS && !use_r && KB <= small_kb) {
-      const dim3 grids((unsigned)ceil_div(N, 128), (unsigned)ceil_div(M, 128));
-      if (bf16_only) hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_BIAS, 1, false, 128, 128>), grids, dim3(512), 0, st, p);
-      else hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_BIAS, 3, false, 128, 128>), grids, dim3(512), 0, st, p);
-    } else if (use_r) {
-#define ONSSEN_XR(T_)                                                                                                 \
-  do {                                                                                                                \
-    if (bm == 256 && bn == 320) hipLaunchKernelGGL((linear_x3r_kernel<T_, 320, 256>), gridq, dim3(512), 0, st, p);    \
-    else if (bm == 256) hipLaunchKernelGGL((linear_x3r_kernel<T_, 256, 256>), gridq, dim3(512), 0, st, p);            \
-    else if (bn == 320) hipLaunchKernelGGL((linear_x3r_kernel<T_, 320, 128>), gridq, dim3(512), 0, st, p);            \
-    else hipLaunchKernelGGL((linear_x3r_kernel<T_, 256, 128>), gridq, dim3(512), 0, st, p);                           \
-  } while (0)
-      if (bf16_only) ONSSEN_XR(1); else ONSSEN_XR(3);
-#undef ONSSEN_XR
-    } else if (mode == ONSSEN_EPI_BIAS) ONSSEN_XQ(ONSSEN_EPI_BIAS);
-    else if (mode == ONSSEN_EPI_L2NORM) {
-      if (bm == 256) { if (bf16_only) hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM, 1, false, 320, 256>), gridq, dim3(512), 0, st, p);
-                       else hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM, 3, false, 320, 256>), gridq, dim3(512), 0, st, p); }
-      else { if (bf16_only) hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM, 1, false, 320, 128>), gridq, dim3(512), 0, st, p);
-             else hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM, 3, false, 320, 128>), gridq, dim3(512), 0, st, p); }
-    } else ONSSEN_XQ(ONSSEN_EPI_SIGMOID);
-#undef ONSSEN_XQ
-#undef ONSSEN_XQ2
-    ONSSEN_LAUNCH_CHECK();
-    return ONSSEN_OK;
-  }
-  static const int xp_wms = ONSSEN_KNOB_INT("ONSSEN_X3P_WAVES", 8) == 4 ? 2 : 4;   // 8 waves unless =4
-  const dim3 grid((unsigned)ceil_div(N, lxp::BN), (unsigned)ceil_div(M, lxp::BM)), block(128 * xp_wms);
-#define ONSSEN_XP(MODE_)                                                                                       \
-  do {                                                                                                         \
-    if (xp_wms == 4 && bf16_only) hipLaunchKernelGGL((linear_x3p_kernel<MODE_, 4, 1>), grid, block, 0, st, p);    \
-    else if (xp_wms == 4) hipLaunchKernelGGL((linear_x3p_kernel<MODE_, 4, 3>), grid, block, 0, st, p);           \
-    else if (bf16_only) hipLaunchKernelGGL((linear_x3p_kernel<MODE_, 2, 1>), grid, block, 0, st, p);             \
-    else hipLaunchKernelGGL((linear_x3p_kernel<MODE_, 2, 3>), grid, block, 0, st, p);                            \
-  } while (0)
-  if (mode == ONSSEN_EPI_BIAS) ONSSEN_XP(ONSSEN_EPI_BIAS);
-  else if (mode == ONSSEN_EPI_L2NORM) ONSSEN_XP(ONSSEN_EPI_L2NORM);
-  else ONSSEN_XP(ONSSEN_EPI_SIGMOID);
-#undef ONSSEN_XP
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-
 size_t onssen_loss_dc_workspace_bytes(int B) {   // partial Grams + (gradient pass) one M matrix and sum(mag) per utterance
   return B > 0 ? (size_t)B * (lossdc::NBLK + 1) * (lossdc::ZMAX * lossdc::ZMAX + 1) * sizeof(float) : 0;
 }
-
-
-int onssen_linear_x3p(const uint16_t* a_img, int M, int K, const uint16_t* w_img, const float* bias, int N, int mode,
-                      int group, float eps, float* C, int R, int64_t c_s0, int64_t c_s1, void* stream) {
-  if ((mode & ~ONSSEN_EPI_BF16) == ONSSEN_EPI_L2NORM && group == 2) return ONSSEN_E_ARG;      // pairs: onssen_linear_x3p_resid
-  return linear_x3p_impl(a_img, M, K, w_img, bias, N, mode, group, eps, nullptr, 0, C, R, c_s0, c_s1, stream);
-}
-
-int onssen_linear_x3p_norms(const uint16_t* a_img, int M, int K, const uint16_t* w_img, const float* bias, int N, int group,
-                            float eps, float* C, float* inv_norm, void* stream) {
-  if (!inv_norm || group <= 2) return ONSSEN_E_ARG;
-  return linear_x3p_impl(a_img, M, K, w_img, bias, N, ONSSEN_EPI_L2NORM, group, eps, nullptr, 0, C, 1, N, 0, stream, inv_norm);
-}
-
-int onssen_linear_x3p_pair(const uint16_t* a_img, int M, int K, const uint16_t* w_img, const float* bias, int N, int n_split,
-                           int group, float eps, float* C, int R, int64_t c_s0, int64_t c_s1, float* C2, int64_t c2_s0,
-                           int64_t c2_s1, int bf16_only, void* stream) {
-  if (!a_img || !w_img || !bias || !C || !C2 || R <= 0 || M <= 0 || K <= 0 || N <= 0) return ONSSEN_E_ARG;
-  if (group <= 0 || (group % 4) != 0 || (80 % group) != 0 || 80 / group > 4) return ONSSEN_E_ARG;
-  if (n_split <= 0 || n_split >= N || (n_split % group) != 0) return ONSSEN_E_ARG;
-  if (!aligned16(a_img) || !aligned16(w_img)) return ONSSEN_E_ALIGN;
-  const int KB = ceil_div(K, 32);
-  if ((long)lxq::BM_MAX * KB * 128 > 0x7fffffffL) return ONSSEN_E_ARG;
-  ONSSEN_CLEAR_ERROR();
-  LinearXpArgs p;
-  p.A = a_img; p.W = w_img; p.bias = bias; p.C = C; p.c_s0 = (long)c_s0; p.c_s1 = (long)c_s1; p.R = R; p.M = M; p.N = N;
-  p.KB = KB; p.group = group; p.eps = eps; p.resid = nullptr; p.r_mod = 1;
-  p.dest = nullptr; p.dest_bs = 0; p.F = 0;
-  p.a_bs = p.w_bs = p.c_bs = 0;
-  p.C2 = C2; p.c2_s0 = (long)c2_s0; p.c2_s1 = (long)c2_s1; p.c2_bs = 0; p.n_split = n_split; p.n_split_odd = 0;
-  p.tile_group = 4;
-  p.c_vec = aligned16(C) && (n_split % 4) == 0 && (c_s0 % 4) == 0 && (c_s1 % 4) == 0;
-  // half-height tiles where 256-row tiles would leave CUs idle (the cost model of onssen_linear_x3p)
-  const long t256 = (long)ceil_div(M, 256) * ceil_div(N, 320), t128 = (long)ceil_div(M, 128) * ceil_div(N, 320);
-  const int bm = (double)ceil_div(t128, 256L) * 128 * 1.15 < (double)ceil_div(t256, 256L) * 256 ? 128 : 256;
-  const dim3 gridq((unsigned)ceil_div(N, 320), (unsigned)ceil_div(M, bm));
-  hipStream_t st = (hipStream_t)stream;
-  if (bm == 256) { if (bf16_only) hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM_SIGMOID, 1, false, 320, 256>), gridq, dim3(512), 0, st, p);
-                   else hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM_SIGMOID, 3, false, 320, 256>), gridq, dim3(512), 0, st, p); }
-  else { if (bf16_only) hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM_SIGMOID, 1, false, 320, 128>), gridq, dim3(512), 0, st, p);
-         else hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM_SIGMOID, 3, false, 320, 128>), gridq, dim3(512), 0, st, p); }
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-int onssen_linear_x3p_compact(const uint16_t* a_img, int M, int K, const uint16_t* w_img, const float* bias, int N, int group,
-                              float eps, const int32_t* dest, int64_t dest_bs, int F, float* comp, int R, int64_t comp_bs,
-                              int bf16_only, void* stream) {
-  if (!a_img || !w_img || !bias || !dest || !comp || R <= 0 || M <= 0 || K <= 0 || N <= 0 || F <= 0) return ONSSEN_E_ARG;
-  if (group <= 0 || (group % 4) != 0 || (80 % group) != 0 || 80 / group > 4 || N != F * group) return ONSSEN_E_ARG;
-  if (!aligned16(a_img) || !aligned16(w_img) || !aligned16(comp) || (comp_bs % 4) != 0) return ONSSEN_E_ALIGN;
-  const int KB = ceil_div(K, 32);
-  if ((long)lxq::BM_MAX * KB * 128 > 0x7fffffffL) return ONSSEN_E_ARG;
-  ONSSEN_CLEAR_ERROR();
-  LinearXpArgs p;
-  p.A = a_img; p.W = w_img; p.bias = bias; p.C = comp; p.c_s0 = 0; p.c_s1 = (long)comp_bs; p.R = R; p.M = M; p.N = N;
-  p.KB = KB; p.group = group; p.eps = eps; p.resid = nullptr; p.r_mod = 1;
-  p.a_bs = p.w_bs = p.c_bs = 0;
-  p.C2 = nullptr; p.c2_s0 = p.c2_s1 = p.c2_bs = 0; p.n_split = 0; p.n_split_odd = 0;
-  p.dest = dest; p.dest_bs = (long)dest_bs; p.F = F;
-  p.tile_group = 4;
-  p.c_vec = 1;
-  // half-height tiles where 256-row tiles would leave CUs idle (the cost model of onssen_linear_x3p)
-  const long t256 = (long)ceil_div(M, 256) * ceil_div(N, 320), t128 = (long)ceil_div(M, 128) * ceil_div(N, 320);
-  const int bm = (double)ceil_div(t128, 256L) * 128 * 1.15 < (double)ceil_div(t256, 256L) * 256 ? 128 : 256;
-  const dim3 gridq((unsigned)ceil_div(N, 320), (unsigned)ceil_div(M, bm));
-  hipStream_t st = (hipStream_t)stream;
-  if (bm == 256) { if (bf16_only) hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM_COMPACT, 1, false, 320, 256>), gridq, dim3(512), 0, st, p);
-                   else hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM_COMPACT, 3, false, 320, 256>), gridq, dim3(512), 0, st, p); }
-  else { if (bf16_only) hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM_COMPACT, 1, false, 320, 128>), gridq, dim3(512), 0, st, p);
-         else hipLaunchKernelGGL((linear_x3q_kernel<ONSSEN_EPI_L2NORM_COMPACT, 3, false, 320, 128>), gridq, dim3(512), 0, st, p); }
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-int onssen_linear_x3p_resid(const uint16_t* a_img, int M, int K, const uint16_t* w_img, const float* bias, int N, int group,
-                            float eps, const float* resid, int resid_mod, float* C, int R, int64_t c_s0, int64_t c_s1,
-                            int bf16_only, void* stream) {
-  if (group != 2 && (group <= 0 || (group % 4) != 0)) return ONSSEN_E_ARG;
-  return linear_x3p_impl(a_img, M, K, w_img, bias, N, ONSSEN_EPI_L2NORM | (bf16_only ? ONSSEN_EPI_BF16 : 0), group, eps, resid,
-                         resid_mod, C, R, c_s0, c_s1, stream);
-}
-
 int onssen_loss_dc_f32(const float* emb, const float* one_hot, const float* mag, int B, int TF, int D, int C,
                        float* per_utt, float* total_mag, void* ws, size_t ws_bytes, void* stream) {
   if (!emb || !one_hot || !mag || !per_utt || !total_mag || !ws || B <= 0 || TF <= 0 || D <= 0 || C <= 0 ||
@@ -1146,9 +707,8 @@ int onssen_phase_input_f32(const float* x_mag, const float* mask, int64_t m_sb, 
                            int64_t m_sf, const float* x_phase, int B, int C, int T, int F, float* out, void* stream) {
   if (!x_mag || !mask || !x_phase || !out || B <= 0 || C <= 0 || T <= 0 || F <= 0) return ONSSEN_E_ARG;
   const long total = (long)C * B * T * 3 * F;
-  const long nb = (total + 255) / 256;
   ONSSEN_CLEAR_ERROR();
-  hipLaunchKernelGGL(phase_input_kernel, dim3((unsigned)(nb > 8192 ? 8192 : nb)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(phase_input_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream,
                      x_mag, mask, (long)m_sb, (long)m_sc, (long)m_st, (long)m_sf, x_phase, B, C, T, F, out);
   ONSSEN_LAUNCH_CHECK();
   return ONSSEN_OK;
@@ -1164,8 +724,7 @@ int onssen_labels_f32(const float* stft_mix, const float* stft_s1, const float* 
   hipStream_t st = (hipStream_t)stream;
   const long per_utt = (long)T * F, total = per_utt * B;
   hipLaunchKernelGGL(utt_max_kernel, dim3((unsigned)B), dim3(256), 0, st, feature_mix, per_utt, utt_max);
-  const long nb = (total + 255) / 256;
-  hipLaunchKernelGGL(labels_kernel, dim3((unsigned)(nb > 8192 ? 8192 : nb)), dim3(256), 0, st, stft_mix, stft_s1, stft_s2,
+  hipLaunchKernelGGL(labels_kernel, dim3(ew_blocks(total)), dim3(256), 0, st, stft_mix, stft_s1, stft_s2,
                      feature_mix, utt_max, per_utt, total, db_threshold, one_hot, mag_mix, mag_s1, mag_s2, cos_s1, cos_s2);
   ONSSEN_LAUNCH_CHECK();
   return ONSSEN_OK;
@@ -1180,8 +739,6 @@ int onssen_param_guard_u32(const void* const* ptrs, const int64_t* numel, int n,
   ONSSEN_LAUNCH_CHECK();
   return ONSSEN_OK;
 }
-
-static unsigned ew_blocks(long total) { const long nb = (total + 255) / 256; return (unsigned)(nb > 8192 ? 8192 : nb); }
 
 int onssen_log_magnitude_f32(const float* stft_ri, int64_t n, float epsilon, float* out, void* stream) {
   if (!stft_ri || !out || n <= 0) return ONSSEN_E_ARG;
