@@ -594,6 +594,28 @@ int onssen_loss_enhance_f32(int mode, const float* est, const float* mag_noisy, 
                             int TF, float scale, float* per_utt, float* total, void* ws, size_t ws_bytes, void* stream);
 int onssen_loss_enhance_grad_f32(int mode, const float* est, const float* mag_noisy, const float* mag_clean, const float* cos_diff,
                                  int B, int TF, float scale, const float* g, float* d_est, void* stream);
+/* uPIT (the permutation-invariant mask network), csrc/loss_upit.inc: the utterance-level mask loss for S = 2 .. 4 speakers.
+ * Per utterance b over its bins, x = mag_mix, m_k the S mask estimates, t_j = mag_s_j (cos_src NULL: MSA) or
+ * min(x, relu(mag_s_j * cos_j)) (PSA):
+ *   pair[b][k][j] = sum_bins |m_k x - t_j|,   total[b][p] = sum_k pair[b][k][p[k]] for the S! assignments p in the order of
+ *   itertools.permutations(range(S)),   out[b] = min_p total[b][p],   perm[b] = the index of that p (of equal totals the smallest).
+ * Mask k at bin e of row b sits at masks[b * m_sb + e * m_se + k * m_ss] (the network's interleaved (B, TF, S) buffer: TF * S, S, 1;
+ * S contiguous maps: TF, 1, B * TF).  mag_mix (B, TF) contiguous; source j's map (B, TF) contiguous at mag_src + j * s_sd,
+ * cos_src + j * c_sd (16-byte loads where the rows are aligned, the same bits where they are not).  frames (nullable, B values,
+ * with F | TF): row b covers its first frames[b] * F bins only -- bit for bit the value of a batch-1 call on them; its gradient
+ * beyond them is written as zero.  perm and pair (B, S, S) may be NULL.  Per-bin terms in fp32 (the residual is one fused
+ * multiply-add), sums in fp64 in a fixed order (no atomics: bit-repeatable).  ws: caller-owned, 8-byte aligned,
+ * onssen_loss_upit_workspace_bytes(B, S) bytes, needs no zeroing.
+ * onssen_loss_upit_grad_f32, one elementwise pass: d_masks (strided like masks; every element written)
+ *   d m_k = g[b] * x * sign(m_k x - t_p[k]),  p = assignment number perm[b];  sign(0) = 0. */
+size_t onssen_loss_upit_workspace_bytes(int B, int S);
+int onssen_loss_upit_f32(const float* masks, int64_t m_sb, int64_t m_se, int64_t m_ss, const float* mag_mix, const float* mag_src,
+                         int64_t s_sd, const float* cos_src, int64_t c_sd, const int32_t* frames, int F, int B, int TF, int S,
+                         float* out, int32_t* perm, float* pair, void* ws, size_t ws_bytes, void* stream);
+int onssen_loss_upit_grad_f32(const float* masks, int64_t m_sb, int64_t m_se, int64_t m_ss, const float* mag_mix,
+                              const float* mag_src, int64_t s_sd, const float* cos_src, int64_t c_sd, const int32_t* frames, int F,
+                              int B, int TF, int S, const float* g, const int32_t* perm, float* d_masks, int64_t d_sb, int64_t d_se,
+                              int64_t d_ss, void* stream);
 size_t onssen_loss_dc_workspace_bytes(int B);
 int onssen_loss_dc_f32(const float* emb, const float* one_hot, const float* mag, int B, int TF, int D, int C,
                        float* per_utt, float* total_mag, void* ws, size_t ws_bytes, void* stream);

@@ -113,6 +113,10 @@ SIGNATURES = {
     "onssen_loss_enhance_workspace_bytes": (_sz, [_i]),
     "onssen_loss_enhance_f32": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "onssen_loss_enhance_grad_f32": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+    "onssen_loss_upit_workspace_bytes": (_sz, [_i, _i]),
+    "onssen_loss_upit_f32": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "onssen_loss_upit_grad_f32": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64,
+                                       _i64, _i64, _vp]),
     "onssen_loss_dc_workspace_bytes": (_sz, [_i]),
     "onssen_batch_sdr_workspace_bytes": (_sz, [_i]),
     "onssen_batch_sdr_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -643,6 +647,18 @@ class Lib:
     def loss_enhance_grad(self, mode, est, mag_noisy, mag_clean, cos_diff, B, TF, scale, g, d_est, stream):
         self.check(self.dll.onssen_loss_enhance_grad_f32(mode, est, mag_noisy, mag_clean, cos_diff, B, TF, scale, g, d_est, stream),
                    "onssen_loss_enhance_grad_f32")
+
+    def loss_upit_workspace_bytes(self, B, S):
+        return int(self.dll.onssen_loss_upit_workspace_bytes(B, S))
+
+    def loss_upit(self, masks, m_sb, m_se, m_ss, mag, src, s_sd, cs, c_sd, frames, F, B, TF, S, out, perm, pair, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_loss_upit_f32(masks, m_sb, m_se, m_ss, mag, src, s_sd, cs, c_sd, frames, F, B, TF, S, out, perm,
+                                                 pair, ws, ws_bytes, stream), "onssen_loss_upit_f32")
+
+    def loss_upit_grad(self, masks, m_sb, m_se, m_ss, mag, src, s_sd, cs, c_sd, frames, F, B, TF, S, g, perm, d, d_sb, d_se, d_ss,
+                       stream):
+        self.check(self.dll.onssen_loss_upit_grad_f32(masks, m_sb, m_se, m_ss, mag, src, s_sd, cs, c_sd, frames, F, B, TF, S, g, perm,
+                                                      d, d_sb, d_se, d_ss, stream), "onssen_loss_upit_grad_f32")
 
     def phase_input(self, x_mag, mask, m_sb, m_sc, m_st, m_sf, x_phase, B, Cn, T, F, out, stream):
         self.check(self.dll.onssen_phase_input_f32(x_mag, mask, m_sb, m_sc, m_st, m_sf, x_phase, B, Cn, T, F, out,

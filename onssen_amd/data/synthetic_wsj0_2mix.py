@@ -11,6 +11,8 @@ the host and yields ``(input_list, label_list)``.  There is no corpus here, so u
     "chimera"   [feature_mix] , [one_hot, mag_mix, mag_s1, mag_s2]
     "chimera++" [feature_mix] , [one_hot, mag_mix, mag_s1, mag_s2, cos_s1, cos_s2]
     "phase"     [feature_mix, phase_mix] , [one_hot, mag_mix, mag_s1, mag_s2, phase_s1, phase_s2]
+    "upit"      [feature_mix] , [mag_mix, mag_s1 .. mag_sS]
+    "upit-psa"  [feature_mix] , [mag_mix, mag_s1 .. mag_sS, cos_s1 .. cos_sS]      (S = feature_options' num_speaker, 2 .. 4; default 2)
     "conv-tasnet", "lstm-tasnet"   time-domain chunks (data/time_domain.py): [mix] , [s1, s2]
 
 ``one_hot`` is float64 like upstream's (np.zeros default, feature_utils.py:86; the losses cast).  Partition "tt" follows
@@ -21,8 +23,11 @@ import numpy as np
 import torch
 
 from ..features import stft_logmag, training_labels
-from ..synthetic import synth_mixture
+from ..synthetic import synth_mixture, synth_mixture_k
 from . import time_domain
+
+
+UPIT_MODELS = ("upit", "upit-psa")
 
 
 class SyntheticWsj02mix:
@@ -45,6 +50,36 @@ class SyntheticWsj02mix:
         self.partition = partition
         self.seed = seed + {"tr": 0, "cv": 10_000, "tt": 20_000}.get(partition, 30_000)
         self.n_samples = self.hop_size * (self.frame_length + 40)     # a little longer than one chunk: crops differ
+        self.num_speaker = 2
+        if model_name in UPIT_MODELS:
+            ns = fo.get("num_speaker", 2) if isinstance(fo, dict) else getattr(fo, "num_speaker", 2)
+            if isinstance(ns, bool) or not isinstance(ns, (int, np.integer)) or not 2 <= ns <= 4:
+                raise ValueError(f"feature_options num_speaker = {ns!r}: the uPIT loaders take 2, 3 or 4")
+            self.num_speaker = int(ns)
+
+    def _mixture(self, seed, n):
+        """(mix, s_1 .. s_S): two speakers as every other model name draws them, more through synth_mixture_k."""
+        if self.num_speaker == 2:
+            return synth_mixture(seed, n, self.sampling_rate, return_sources=True)
+        return synth_mixture_k(seed, n, self.sampling_rate, self.num_speaker)
+
+    def _iter_upit(self):
+        from ..features import enhance_labels
+        rng = np.random.default_rng(self.seed)
+        B, L, C = self.batch_size, self.frame_length, 1 + self.num_speaker
+        for it in range(self.num_batches):
+            utts = [self._mixture(self.seed + it * B + b, self.n_samples) for b in range(B)]
+            wav = torch.from_numpy(np.stack([np.stack(u) for u in utts])).to(self.device)       # (B, 1 + S, n)
+            logmag, ri = stft_logmag(wav.view(C * B, -1), self.window_size, self.hop_size)
+            T, F = logmag.shape[1], logmag.shape[2]
+            logmag, ri = logmag.view(B, C, T, F), ri.view(B, C, T, F, 2)
+            start = int(rng.integers(0, T - L))
+            feat = logmag[:, 0, start:start + L].contiguous()
+            mix = ri[:, 0, start:start + L].contiguous()
+            # one enhance_labels call per source: (|mix|, |s_k|, cos(angle mix - angle s_k)); a fused S-source kernel is not built
+            labs = [enhance_labels(mix, ri[:, 1 + k, start:start + L].contiguous(), with_cos=self.model_name == "upit-psa")
+                    for k in range(self.num_speaker)]
+            yield [feat], [labs[0][0]] + [l[1] for l in labs] + ([l[2] for l in labs] if self.model_name == "upit-psa" else [])
 
     def __len__(self):
         return self.num_batches
@@ -66,14 +101,14 @@ class SyntheticWsj02mix:
     def _iter_eval(self):
         for it in range(self.num_batches):
             n = self.hop_size * (self.frame_length + 17 * (it % 3)) + 5 * it          # utterances differ in length
-            mix, s1, s2 = synth_mixture(self.seed + it, n, self.sampling_rate, return_sources=True)
+            mix, *srcs = self._mixture(self.seed + it, n)
             gap = 32 - n % 32                                                          # get_sigs (wsj0_2mix.py:216-228)
             pad = lambda a: np.pad(a, (0, gap))
             # the STFT of the file AS IT IS (get_stft(fn), wsj0_2mix.py:231-233); only the reference signals are padded to a
             # multiple of 32 samples (get_sigs, :216-228) -- the estimate is then istft(..., length = padded length)
             wav = torch.from_numpy(np.ascontiguousarray(mix)[None]).to(self.device)
             logmag, ri = stft_logmag(wav, self.window_size, self.hop_size)
-            sig_ref = torch.from_numpy(np.stack([pad(s1), pad(s2)])[None]).to(self.device)
+            sig_ref = torch.from_numpy(np.stack([pad(s) for s in srcs])[None]).to(self.device)
             yield [logmag], [ri[..., 0].contiguous(), ri[..., 1].contiguous(), sig_ref]
 
     def __iter__(self):
@@ -82,6 +117,9 @@ class SyntheticWsj02mix:
             return
         if self.partition == "tt":
             yield from self._iter_eval()
+            return
+        if self.model_name in UPIT_MODELS:
+            yield from self._iter_upit()
             return
         rng = np.random.default_rng(self.seed)
         B, L = self.batch_size, self.frame_length

@@ -15,6 +15,7 @@ and ONE label-kernel launch (``onssen_labels_f32``).  Same
     "chimera"   [feature_mix] , [one_hot, mag_mix, mag_s1, mag_s2]
     "chimera++" [feature_mix] , [one_hot, mag_mix, mag_s1, mag_s2, cos_s1, cos_s2]
     "phase"     [feature_mix, phase_mix] , [one_hot, mag_mix, mag_s1, mag_s2, phase_s1, phase_s2]
+    "upit"      [feature_mix] , [mag_mix, mag_s1, mag_s2]          "upit-psa": + [cos_s1, cos_s2]   (two speakers: the tree has s1 and s2)
 
 Partitions "tr" / "cv": batches of ``batch_size`` in shuffled order (the reference's ``DataLoader(shuffle=True)``), an
 utterance of at most ``frame_length`` frames is repeated ``frame_length // T + 1`` times before the crop (``:118-123``).
@@ -113,9 +114,12 @@ class Wsj02mixFiles:
     def __init__(self, model_name, feature_options, partition="tr", device="cuda:0", shuffle=None, seed=None):
         fo = feature_options
         g = (lambda k: fo[k]) if isinstance(fo, dict) else (lambda k: getattr(fo, k))
-        if model_name not in ("dc", "chimera", "chimera++", "phase") + time_domain.MODELS:
+        if model_name not in ("dc", "chimera", "chimera++", "phase", "upit", "upit-psa") + time_domain.MODELS:
             raise ValueError(f"unknown model_name {model_name!r}")
         self.model_name = model_name
+        ns = fo.get("num_speaker", 2) if isinstance(fo, dict) else getattr(fo, "num_speaker", 2)
+        if model_name in ("upit", "upit-psa") and ns != 2:
+            raise ValueError(f"feature_options num_speaker = {ns!r}: the mix/s1/s2 file tree holds two speakers")
         if model_name in time_domain.MODELS:     # time-domain chunks (data/time_domain.py): no STFT settings
             self.batch_size, self.sampling_rate, self.chunk_size = time_domain.options_of(model_name, fo)
             self.device = torch.device(device if device is not None else "cuda:0")
@@ -308,10 +312,12 @@ class Wsj02mixFiles:
             logmag, ri = self._device_batch(item)                   # (B, 3, L, F), (B, 3, L, F, 2)
             feat = logmag[:, 0].contiguous()
             mix, s1, s2 = (ri[:, i].contiguous() for i in range(3))
-            out = training_labels(mix, s1, s2, feat, self.db_threshold, with_cos=self.model_name == "chimera++")
+            out = training_labels(mix, s1, s2, feat, self.db_threshold, with_cos=self.model_name in ("chimera++", "upit-psa"))
             one_hot, mm, m1, m2 = out[:4]
             one_hot = one_hot.double()                             # np.zeros default dtype upstream (feature_utils.py:86)
-            if self.model_name == "dc":
+            if self.model_name in ("upit", "upit-psa"):            # the chimera labels without one_hot
+                yield [feat], [mm, m1, m2] + list(out[4:6])
+            elif self.model_name == "dc":
                 yield [feat], [one_hot, mm]
             elif self.model_name == "chimera":
                 yield [feat], [one_hot, mm, m1, m2]

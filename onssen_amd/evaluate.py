@@ -298,6 +298,23 @@ class tester_chimera(tester):
         return mask_istft(ri, masks, self.hop_size, sig_ref.shape[-1], frames=frames, lengths=lengths), sig_ref.float()
 
 
+class tester_upit(tester):
+    """The uPIT mask network (upstream has no evaluation for it) on the evaluation loader: the item is the chimera one with
+    ``sig_ref (B,S,n)``, S = 2 .. 4; the network's S masks, mask-apply + iSTFT.  ``eval(batch=K)`` is the base class's ragged
+    loop."""
+
+    def __init__(self, args, hop_size=64):
+        super().__init__(args)
+        self.hop_size = hop_size
+
+    def get_est_sig(self, input, label, output, frames=None, lengths=None):
+        from .features import mask_istft
+        from .loss import _upit_masks_base
+        ri, sig_ref = _mix_ri(label)
+        masks = _upit_masks_base(list(output))            # the network's (B,T,F,S) buffer when the masks are its planes
+        return mask_istft(ri, masks, self.hop_size, sig_ref.shape[-1], frames=frames, lengths=lengths), sig_ref.float()
+
+
 class tester_phase(tester):
     """The phase network on the evaluation loader: the item is the chimera one (``[feature_mix]``, ``[stft_r_mix, stft_i_mix,
     sig_ref]``), the network's second input is rebuilt from its labels, and the estimate is the inverse transform of

@@ -10,6 +10,8 @@ The phase network's loss (``loss_phase``): the same deep-clustering term, and th
 ``onssen_loss_phase_f32`` / ``onssen_loss_phase_grad_f32`` (one pass over the eleven maps forward, one elementwise pass backward).
 The enhancement losses (``loss_mask_msa`` / ``loss_mask_psa``, onssen/loss/loss_mask.py): one estimate against one target, value from
 ``onssen_loss_enhance_f32`` and gradient from ``onssen_loss_enhance_grad_f32`` (csrc/enhance.inc), routed like the chimera losses.
+The uPIT losses (``loss_upit_msa`` / ``loss_upit_psa``; upstream has none): the permutation-invariant mask loss for 2 .. 4 speakers on
+``onssen_loss_upit_f32`` / ``onssen_loss_upit_grad_f32`` (csrc/loss_upit.inc), routed the same way.
 Semantics follow onssen/loss/loss_dc.py:6-44 and loss_util.py:4-11 exactly,
 including their quirks: the affinity terms are Frobenius *norms* (not squared
 norms) and the final product ``(B,) * (B,1)`` broadcasts to a (B, B) tensor
@@ -373,6 +375,164 @@ def loss_mask_psa(output, label):
         last_enhance_path = "aten"
         return _l1(mask * mag_noisy - torch.min(mag_noisy, torch.relu(mag_clean * cos_diff)))
     return _enhance_hip(_abi.ENHANCE_PSA, route, mask, mag_noisy, mag_clean, cos_diff, 1.0)
+
+
+# ----------------------------------------------------------------------------- uPIT losses (2 .. 4 speakers)
+last_upit_path = None
+UPIT_MAX_SPEAKERS = 4                 # upit::SMAX
+
+
+def _upit_aten(masks, mag_mix, targets):
+    """The plain restatement on PyTorch ops: the pair matrix by broadcasting, then the minimum over itertools.permutations (the
+    first minimum wins).  Returns (out (B,), perm (B,) int64)."""
+    from itertools import permutations
+    S = len(masks)
+    est = torch.stack([m * mag_mix for m in masks], 1)                       # (B, S, ...)
+    tgt = torch.stack(list(targets), 1)
+    pair = (est.unsqueeze(2) - tgt.unsqueeze(1)).abs().flatten(3).sum(-1)    # (B, S, S): pair[b][k][j]
+    totals = torch.stack([sum(pair[:, k, p[k]] for k in range(S)) for p in permutations(range(S))], 1)
+    out = totals.min(dim=1).values
+    # torch.min's index among equal values is unspecified: take the first occurrence, as the kernels do
+    perm = (totals == out.unsqueeze(1)).int().argmax(dim=1)
+    return out, perm
+
+
+def _upit_masks_base(masks):
+    """The contiguous (..., S) fp32 buffer whose S planes the masks are (the network's own when all are views of one, as
+    _mask_term_hip_autograd checks for two; anything else is interleaved by torch.stack)."""
+    S, m0 = len(masks), masks[0]
+    base = getattr(m0, "_base", None)
+    dense, acc = [], S
+    for n_i in reversed(m0.shape):
+        dense.insert(0, acc)
+        acc *= n_i
+    if (base is not None and base.dtype == torch.float32 and base.is_contiguous() and base.numel() == S * m0.numel()
+            and all(getattr(m, "_base", None) is base and m.stride() == tuple(dense) and m.shape == m0.shape
+                    and m.storage_offset() == base.storage_offset() + k for k, m in enumerate(masks))):
+        return base.view(*m0.shape, S)          # (the root may be the head's (B, T, F S) output: the same memory)
+    return torch.stack([m.float() for m in masks], -1)
+
+
+def _upit_maps(maps):
+    """S label maps of one shape -> (first pointer's tensor list kept alive, pointer, distance in floats): the maps as they lie
+    when they sit at one common distance (slices of one tensor, say), else stacked first."""
+    maps = [t.detach().float().contiguous() for t in maps]
+    ptrs = [t.data_ptr() for t in maps]
+    d = ptrs[1] - ptrs[0]
+    if d % 4 == 0 and all(ptrs[j] - ptrs[0] == j * d for j in range(len(maps))):
+        return maps, ptrs[0], d // 4
+    st = torch.stack(maps, 0)
+    return [st], st.data_ptr(), maps[0].numel()
+
+
+def _upit_frames(frames, B, T, device):
+    if frames is None:
+        return None
+    from .nn._core import as_frames
+    return as_frames(frames, B, T, device)
+
+
+def _upit_launch(base, S, mag, src, cs, frames, F, want_perm=True):
+    from .hip import get_lib
+    lib = get_lib()
+    B, TF, dev = mag.shape[0], mag[0].numel(), mag.device
+    out = torch.empty(B, device=dev, dtype=torch.float32)
+    perm = torch.empty(B, device=dev, dtype=torch.int32)
+    ws = torch.empty(lib.loss_upit_workspace_bytes(B, S), dtype=torch.uint8, device=dev)
+    lib.loss_upit(base.data_ptr(), TF * S, S, 1, mag.data_ptr(), src[1], src[2], cs[1] if cs else None, cs[2] if cs else 0,
+                  frames.data_ptr() if frames is not None else None, F, B, TF, S, out.data_ptr(), perm.data_ptr(), None,
+                  ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    return out, perm
+
+
+class _UpitLossHip(torch.autograd.Function):
+    """The uPIT mask loss with the masks' gradient on the device (csrc/loss_upit.inc): ``onssen_loss_upit_f32`` picks the
+    assignment per utterance in the forward pass, ``onssen_loss_upit_grad_f32`` writes d/d masks in one elementwise pass.
+    ``base`` is the interleaved (B, ..., S) buffer (see _MaskTermHip); the labels carry no gradient.  Returns (out, perm)."""
+
+    @staticmethod
+    def forward(ctx, base, S, mag, src, cs, frames, F):
+        out, perm = _upit_launch(base, S, mag, src, cs, frames, F)
+        ctx.save_for_backward(base, mag, perm, *src[0], *(cs[0] if cs else []), *([frames] if frames is not None else []))
+        ctx.geom = (S, src[1:], cs[1:] if cs else None, frames is not None, F)
+        ctx.mark_non_differentiable(perm)
+        return out, perm
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_perm):
+        from .hip import get_lib
+        S, src, cs, ragged, F = ctx.geom
+        base, mag, perm, *rest = ctx.saved_tensors
+        frames = rest[-1] if ragged else None
+        B, TF = mag.shape[0], mag[0].numel()
+        d = torch.empty_like(base)
+        g = g.float().contiguous()
+        get_lib().loss_upit_grad(base.data_ptr(), TF * S, S, 1, mag.data_ptr(), src[0], src[1], cs[0] if cs else None,
+                                 cs[1] if cs else 0, frames.data_ptr() if ragged else None, F, B, TF, S, g.data_ptr(),
+                                 perm.data_ptr(), d.data_ptr(), TF * S, S, 1, torch.cuda.current_stream().cuda_stream)
+        return d, None, None, None, None, None, None
+
+
+def _loss_upit(name, output, label, psa, frames, return_perm):
+    global last_upit_path
+    masks = list(output)
+    S = len(masks)
+    want = 1 + (2 if psa else 1) * S
+    if S < 2 or len(label) != want:
+        raise ValueError(f"{name}: {len(label)} label tensors for {S} masks; {S} masks take {want} "
+                         f"([mag_mix, mag_s1 .. mag_s{S}" + (f", cos_s1 .. cos_s{S}])" if psa else "])"))
+    mag_mix, mags, coss = label[0], list(label[1:1 + S]), (list(label[1 + S:]) if psa else None)
+    m0 = masks[0]
+    needs_grad = not _no_grad_needed(*masks)
+    same = all(t.shape == m0.shape for t in masks + [mag_mix] + mags + (coss or []))
+    if not m0.is_cuda or S > UPIT_MAX_SPEAKERS or not same or m0.dim() < 2:
+        route = "aten"
+    elif not needs_grad:
+        route = "value"
+    else:
+        route = "grad" if options.get("loss") == "1" else "aten"
+    last_upit_path = route
+    if route == "aten":
+        if frames is not None:
+            raise RuntimeError(f"{name}: frames=... (ragged batch) needs the HIP kernels (ROCm tensors, at most "
+                               f"{UPIT_MAX_SPEAKERS} speakers, option loss = \"1\" when a gradient is wanted)")
+        mag = mag_mix.detach()
+        tg = [t.detach() for t in mags] if not psa else [torch.min(mag, torch.relu(s.detach() * c.detach()))
+                                                         for s, c in zip(mags, coss)]
+        out, perm = _upit_aten(masks, mag, tg)
+        return (out, perm) if return_perm else out
+    B = m0.shape[0]
+    F = m0.shape[-1]
+    frames = _upit_frames(frames, B, m0[0].numel() // F, m0.device)
+    mag = mag_mix.detach().float().contiguous()
+    src, cs = _upit_maps(mags), (_upit_maps(coss) if psa else None)
+    base = _upit_masks_base(masks)
+    if route == "grad":
+        out, perm = _UpitLossHip.apply(base, S, mag, src, cs, frames, F)
+    else:
+        out, perm = _upit_launch(base.detach(), S, mag, src, cs, frames, F)
+    return (out, perm.long()) if return_perm else out
+
+
+def loss_upit_msa(output, label, frames=None, return_perm=False):
+    """Utterance-level permutation-invariant mask loss, magnitude spectrum approximation, for S = len(output) speakers (upstream
+    has the uPIT network, onssen/nn/uPIT-LSTM.py, and no loss for it): ``output`` = the S masks (B,T,F), ``label`` = [mag_mix,
+    mag_s1 .. mag_sS].  Per utterance ``min_p sum_k sum_bins |m_k mag_mix - mag_s_p[k]|`` over the S! assignments p, (B,) -- the
+    trainer takes the mean; for S = 2 the mask term of ``loss_chimera_msa``.  ``return_perm``: also the index (B,) int64 of each
+    row's assignment in the order of ``itertools.permutations(range(S))`` (the first minimum wins).  ``frames`` (B,): a ragged
+    batch, row b is its first frames[b] frames (HIP kernels only).
+
+    On ROCm tensors the value comes from ``onssen_loss_upit_f32`` when no gradient is wanted, value and gradient from the autograd
+    node over the two kernels (csrc/loss_upit.inc) with option ``loss`` = "1"; otherwise -- CPU tensors, ``loss`` = "torch", more
+    than four speakers -- PyTorch ops.  ``last_upit_path`` ("value" | "grad" | "aten") says which route the last call took."""
+    return _loss_upit("loss_upit_msa", output, label, False, frames, return_perm)
+
+
+def loss_upit_psa(output, label, frames=None, return_perm=False):
+    """As ``loss_upit_msa`` with the phase-sensitive targets ``min(mag_mix, relu(mag_s_j cos_s_j))``: ``label`` = [mag_mix,
+    mag_s1 .. mag_sS, cos_s1 .. cos_sS]; for S = 2 the mask term of ``loss_chimera_psa``."""
+    return _loss_upit("loss_upit_psa", output, label, True, frames, return_perm)
 
 
 # ----------------------------------------------------------------------------- phase network loss

@@ -6,5 +6,6 @@ from .deep_clustering import deep_clustering
 from .enhancement import enhance
 from .phase_network import phase_net
 from .tasnet import ConvTasNet
+from .upit import uPIT_LSTM
 
-__all__ = ["chimera", "deep_clustering", "enhance", "phase_net", "ConvTasNet"]
+__all__ = ["chimera", "deep_clustering", "enhance", "phase_net", "ConvTasNet", "uPIT_LSTM"]

@@ -35,6 +35,21 @@ def separate_chimera(model, wav, window_size=256, hop_size=64, lengths=None):
 
 @recovering
 @torch.no_grad()
+def separate_upit(model, wav, window_size=256, hop_size=64, lengths=None):
+    """wav (B, n) cuda float32 -> (B, S, n), S = ``model.num_speaker`` (2 .. 4): STFT -> ``uPIT_LSTM.masks`` -> ``mask_istft``.
+    Nothing is read back by the host, so a call can be captured in a hipGraph.  ``lengths`` (B,): a ragged batch of whole
+    utterances padded to n samples; every row inside its own length is bit for bit its batch-1 result, zeros after it (see
+    separate_dc)."""
+    lengths, frames = _ragged(wav, lengths, hop_size)
+    logmag, ri = stft_logmag(wav, window_size, hop_size, lengths=lengths)
+    masks = model.masks(logmag, frames)
+    out = mask_istft(ri, masks, hop_size, wav.shape[-1], frames=frames, lengths=lengths)
+    _XcdStatus.flush()            # an aborted recurrence is caught HERE (and the call re-run, see `recovering`), not by the next call
+    return out
+
+
+@recovering
+@torch.no_grad()
 def separate_phase(model, wav, window_size=256, hop_size=64):
     """wav (B, n) cuda float32 -> (B, 2, n): phase_net's masks AND its phase estimates go into the inverse transform
     (features.phase_istft); the mixture's phase is only the network's input.  Uniform batches (phase_net has no ragged forward)."""

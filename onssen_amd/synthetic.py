@@ -25,7 +25,7 @@ def lstm_param_shapes(in_dim, H, L, prefix="rnn."):
 def make_state_dict(kind, input_dim, hidden_dim, num_layers, embedding_dim=20,
                     num_speaker=2, seed=0, gain=1.0):
     """Reference-layout state_dict (numpy float32) for ``kind`` in
-    {"deep_clustering", "chimera", "phase_net", "enhance"}.
+    {"deep_clustering", "chimera", "phase_net", "enhance", "upit"}.
 
     LSTM / Linear tensors ~ U(-1/sqrt(fan), 1/sqrt(fan)) like PyTorch's default
     init (times ``gain``); BatchNorm affine and running statistics are drawn
@@ -74,6 +74,9 @@ def make_state_dict(kind, input_dim, hidden_dim, num_layers, embedding_dim=20,
         linear("fc_mi.", F, 2 * H)
         linear("fc_pre.", F, F)
         linear("fc_post.", F, F)
+    elif kind == "upit":
+        lstm("rnn.", F)
+        linear("fc_mi.", F * C, 2 * H)
     else:
         raise ValueError(kind)
     return sd
@@ -118,6 +121,27 @@ def synth_mixture(seed, n_samples=25536, sr=8000, return_sources=False):
         return ((mix * scale).astype(np.float32), (s1 * scale).astype(np.float32),
                 (s2 * scale).astype(np.float32))
     return (mix * scale).astype(np.float32)
+
+
+def synth_mixture_k(seed, n_samples=25536, sr=8000, num_speaker=2):
+    """(mix, s_1 .. s_S) float32, peak 0.9: ``synth_mixture`` for ``num_speaker`` voices.  Drawn as there: every further
+    speaker is levelled against s_1 from U(-2.5, 2.5) dB right after its voice, then the noise floor against the clean sum.
+    For two speakers the result is ``synth_mixture(..., return_sources=True)`` bit for bit."""
+    if num_speaker < 2:
+        raise ValueError(f"synth_mixture_k: num_speaker = {num_speaker}, a mixture has at least two")
+    rng = np.random.default_rng(seed)
+    srcs = [_speaker(rng, n_samples, sr)]
+    for _ in range(1, num_speaker):
+        s = _speaker(rng, n_samples, sr)
+        s *= 10 ** (rng.uniform(-2.5, 2.5) / 20) * (np.std(srcs[0]) + 1e-9) / (np.std(s) + 1e-9)
+        srcs.append(s)
+    clean = srcs[0] + srcs[1]
+    for s in srcs[2:]:
+        clean = clean + s
+    noise = rng.normal(0, 1, n_samples) * max(1e-2 * np.std(clean), 1e-4)   # never an all-zero mixture
+    mix = clean + noise
+    scale = 0.9 / np.max(np.abs(mix))
+    return ((mix * scale).astype(np.float32),) + tuple((s * scale).astype(np.float32) for s in srcs)
 
 
 def synth_batch(config_id, batch, n_samples=25536, sr=8000):
