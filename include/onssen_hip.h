@@ -985,6 +985,37 @@ size_t onssen_tasnet_stitch_workspace_bytes(int C, int K, int W, int step, int v
 int onssen_tasnet_stitch_f32(const float* est, int C, int K, int W, int step, int v_last, float* out, int32_t* perm_out, void* ws,
                              size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sample-rate conversion of the file loaders, csrc/resample.inc: scipy.signal.resample_poly(x, up, down) with its default
+ * window, over a ragged batch, in one launch.  up = rate_out / g, down = rate_in / g (g their gcd; every entry reduces the pair
+ * it is given), M = max(up, down) <= 2048, half = 10 M, taps h[0 .. 2 half]:
+ *   g[k] = sinc((k - half) / M) I0(5 sqrt(1 - ((k - half) / half)^2)) / I0(5),  h = up g / sum g,  sinc(t) = sin(pi t) / (pi t)
+ *   n_out = ceil(n_in up / down),  y[m] = sum_n x[n] h[m down - n up + half] over the n in [0, n_in) whose tap index is in range.
+ *   Equal rates are the identity: half = 0 and the one tap 1.0 (resample_poly returns a copy).
+ * onssen_resample_geometry: the reduced pair, half and n_out of (rate_in, rate_out, n_in); outputs may be NULL.  Host only.
+ * onssen_resample_taps_f64: the 2 half + 1 taps into HOST memory, fp64, computed by the library (no SciPy behind the C ABI).
+ * onssen_resample_workspace_bytes / onssen_resample_prepare: the device image of the taps, phase-major -- up rows of
+ *   L = ceil((2 half + 1) / up) fp64 values, row p = h[p], h[p + up], ... (0 beyond 2 half), so that one output reads its L taps
+ *   contiguously -- into caller-owned, 16-byte aligned device memory.  prepare computes on the host and copies with a BLOCKING
+ *   copy: once per ratio, outside any graph capture; `stream` is unused.
+ * onssen_resample_f32: x = B rows stride_in floats apart, row b holding lengths_in[b] <= n_in samples (lengths_in NULL: n_in
+ *   each; device int32 values, clamped to [0, n_in]); sub (nullable, laid out like x): the filter's input is x - sub, formed in
+ *   fp64 on load (onssen/data/feature_utils.py:24-33, get_stft_from_subtraction, in the same pass).  y = B rows stride_out
+ *   floats apart: row b gets ceil(lengths_in[b] up / down) samples and ZEROS from there to stride_out; lengths_out (nullable,
+ *   device int32, B values) receives that count.  Nothing at or beyond lengths_in[b] is read.  Products and sum in fp64 in a
+ *   fixed order, one rounding to fp32 at the store, no atomics: bit-repeatable, and a row's output is bit for bit that of a
+ *   batch-1 call on it.  Index arithmetic is 64-bit (m down may pass 2^31).  One launch on `stream`: nothing is allocated, nothing
+ *   synchronises, capturable into a graph.  ws: what onssen_resample_prepare filled for the same ratio.
+ * ONSSEN_E_ARG, before anything is launched or written: up or down < 1, a reduced up or down above 2048, a NULL x / y / ws,
+ *   B outside 1 .. 65535, n_in < 1, stride_in < n_in, stride_out < ceil(n_in up / down), ws_bytes below
+ *   onssen_resample_workspace_bytes (which is 0 for a refused ratio).  ONSSEN_E_ALIGN: ws not 16-byte aligned. */
+int onssen_resample_geometry(int rate_in, int rate_out, int64_t n_in, int* up, int* down, int* half, int64_t* n_out);
+int onssen_resample_taps_f64(int up, int down, double* taps_host);
+size_t onssen_resample_workspace_bytes(int up, int down);
+int onssen_resample_prepare(int up, int down, void* ws, size_t ws_bytes, void* stream);
+int onssen_resample_f32(const float* x, const float* sub, int64_t stride_in, const int32_t* lengths_in, int B, int n_in, int up,
+                        int down, float* y, int64_t stride_out, int32_t* lengths_out, const void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,12 @@ SIGNATURES = {
     "onssen_loss_upit_f32": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "onssen_loss_upit_grad_f32": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64,
                                        _i64, _i64, _vp]),
+    # sample-rate conversion of the file loaders (csrc/resample.inc)
+    "onssen_resample_geometry": (_i, [_i, _i, _i64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64)]),
+    "onssen_resample_taps_f64": (_i, [_i, _i, _vp]),
+    "onssen_resample_workspace_bytes": (_sz, [_i, _i]),
+    "onssen_resample_prepare": (_i, [_i, _i, _vp, _sz, _vp]),
+    "onssen_resample_f32": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
     "onssen_loss_dc_workspace_bytes": (_sz, [_i]),
     "onssen_batch_sdr_workspace_bytes": (_sz, [_i]),
     "onssen_batch_sdr_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -647,6 +653,33 @@ class Lib:
     def loss_enhance_grad(self, mode, est, mag_noisy, mag_clean, cos_diff, B, TF, scale, g, d_est, stream):
         self.check(self.dll.onssen_loss_enhance_grad_f32(mode, est, mag_noisy, mag_clean, cos_diff, B, TF, scale, g, d_est, stream),
                    "onssen_loss_enhance_grad_f32")
+
+    # ---- sample-rate conversion (scipy.signal.resample_poly on the device) -------------
+    def resample_geometry(self, rate_in, rate_out, n_in):
+        """(up, down, half, n_out) of a conversion of n_in samples: the reduced ratio, the filter's half length, ceil(n_in up / down)."""
+        up, down, half, n_out = _i(), _i(), _i(), _i64()
+        self.check(self.dll.onssen_resample_geometry(rate_in, rate_out, n_in, up, down, half, n_out), "onssen_resample_geometry")
+        return up.value, down.value, half.value, n_out.value
+
+    def resample_taps(self, up, down):
+        """The 2 half + 1 fp64 taps of a ratio as a ctypes array of doubles (host memory)."""
+        g = self.resample_geometry(down, up, 0)
+        taps = (C.c_double * (2 * g[2] + 1))()
+        self.check(self.dll.onssen_resample_taps_f64(up, down, taps), "onssen_resample_taps_f64")
+        return taps
+
+    def resample_workspace_bytes(self, up, down):
+        nb = int(self.dll.onssen_resample_workspace_bytes(up, down))
+        if nb == 0:
+            self.check(-1, "onssen_resample_workspace_bytes")
+        return nb
+
+    def resample_prepare(self, up, down, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_resample_prepare(up, down, ws, ws_bytes, stream), "onssen_resample_prepare")
+
+    def resample(self, x, sub, stride_in, lengths_in, B, n_in, up, down, y, stride_out, lengths_out, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_resample_f32(x, sub, stride_in, lengths_in, B, n_in, up, down, y, stride_out, lengths_out, ws,
+                                                ws_bytes, stream), "onssen_resample_f32")
 
     def loss_upit_workspace_bytes(self, B, S):
         return int(self.dll.onssen_loss_upit_workspace_bytes(B, S))

@@ -26,6 +26,8 @@
 //   enhance.inc         labels_enhance_kernel (|X|, |S|, cos of the phase difference in one pass), loss_enhance_* (the MSA / PSA
 //                       enhancement losses: value and gradient); the reconstruction is mask_istft_kernel's magnitude mode (fft.inc)
 //   loss_upit.inc       loss_upit_* (the uPIT mask network's loss for 2 .. 4 speakers: pair sums in one pass, assignment scan, gradient)
+//   resample.inc        resample_kernel (the loaders' sample-rate conversion: scipy's resample_poly as a polyphase filter over a ragged batch,
+//                       the tile's input span staged in the LDS as fp64, optional subtraction of a second signal on load)
 //   pack.inc            one-off weight re-layout (gate permutation, MFMA fragment order, BatchNorm fold); training glue: dropout,
 //                       row-wise L2 normalisation and train-mode BatchNorm with their backward passes
 #include <hip/hip_runtime.h>
@@ -139,6 +141,7 @@ static unsigned& xcd_spin_limit() {
 #include "loss_phase.inc" // phase_net training: mask term + phase term of loss_phase in one pass, and their gradient
 #include "enhance.inc"    // speech enhancement: training labels, the MSA / PSA losses and their gradient
 #include "loss_upit.inc"  // uPIT training: the utterance-level permutation-invariant mask loss for 2 .. 4 speakers and its gradient
+#include "resample.inc"   // file loaders: polyphase sample-rate conversion (scipy.signal.resample_poly) of a ragged batch
 
 // Co-tenant probe (tools/cotenant_probe.py): `workgroups` workgroups of `threads` threads that do nothing but hold their
 // CU for `ticks` ticks of the 100 MHz wall clock -- a stand-in for RCCL's channel kernels next to the persistent recurrences.

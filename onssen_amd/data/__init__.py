@@ -9,15 +9,19 @@ features and labels are computed on the GPU and the yield contract is the refere
 ``daps_enhance_dataloader`` (onssen/data/daps_enhance.py:30-35; data/daps_enhance.py here) follows the same rule with its list file
 ``<data_path>/<partition>``.
 
-``feature_utils`` carries the reference's helper names (``get_stft``, ``get_log_magnitude``, ``get_phase``, ``get_cos_difference``,
+``edinburgh_tts_dataloader`` (onssen/data/edinburgh_tts.py:10-15; data/edinburgh_tts.py here) likewise: list file ``<data_path>/<partition>``,
+noisy / clean trees, the 48 kHz files resampled on the device (``features.resample``).
+
+``feature_utils`` carries the reference's helper names (``get_stft``, ``get_stft_from_subtraction``, ``get_log_magnitude``, ``get_phase``, ``get_cos_difference``,
 ``get_one_hot``: onssen/data/feature_utils.py:5-21,49-95), NumPy in / NumPy out over the same device kernels."""
 import glob
 import os
 
 from .. import options
 from . import feature_utils
-from .feature_utils import get_cos_difference, get_log_magnitude, get_one_hot, get_phase, get_stft
+from .feature_utils import get_cos_difference, get_log_magnitude, get_one_hot, get_phase, get_stft, get_stft_from_subtraction
 from .daps_enhance import DapsEnhanceFiles, SyntheticDapsEnhance, daps_enhance_dataloader
+from .edinburgh_tts import EdinburghTtsFiles, SyntheticEdinburghTts, edinburgh_tts_dataloader
 from .synthetic_wsj0_2mix import SyntheticVoicePairs, SyntheticWsj02mix
 from .wsj0_2mix import Wsj02mixFiles, read_wav, write_wav
 
@@ -36,5 +40,6 @@ def wsj0_2mix_dataloader(model_name, feature_options, partition, device=None):
                             f"{partition!r}); pass data_path='' / 'synthetic' or set ONSSEN_SYNTHETIC_DATA=1 for the synthetic corpus")
 
 
-__all__ = ["wsj0_2mix_dataloader", "daps_enhance_dataloader", "DapsEnhanceFiles", "SyntheticDapsEnhance", "feature_utils", "get_stft", "get_log_magnitude", "get_phase", "get_cos_difference", "get_one_hot",
+__all__ = ["wsj0_2mix_dataloader", "daps_enhance_dataloader", "DapsEnhanceFiles", "SyntheticDapsEnhance", "edinburgh_tts_dataloader",
+           "EdinburghTtsFiles", "SyntheticEdinburghTts", "feature_utils", "get_stft", "get_stft_from_subtraction", "get_log_magnitude", "get_phase", "get_cos_difference", "get_one_hot",
            "SyntheticVoicePairs", "SyntheticWsj02mix", "Wsj02mixFiles", "read_wav", "write_wav"]

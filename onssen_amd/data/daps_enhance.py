@@ -21,8 +21,12 @@ Without a tree the rule of ``onssen_amd.data`` applies: the synthetic corpus (``
 ``data_path`` is absent / ``""`` / ``"synthetic"`` or ``ONSSEN_SYNTHETIC_DATA=1`` is set; a ``data_path`` that is given but holds
 no list file for the partition raises ``FileNotFoundError``.
 
-Not here: ``edinburgh_tts_dataloader``, ``get_stft_from_subtraction`` and log-mel features.  Resampling is
-``scipy.signal.resample_poly`` (see data/wsj0_2mix.py)."""
+A file whose rate differs from ``sampling_rate`` (DAPS is a 44.1 kHz corpus) is resampled by ``scipy.signal.resample_poly`` on
+the host (see data/wsj0_2mix.py), or -- option ``loader_resample = "hip"`` -- the noisy / clean pair goes to the device at its own
+rate in one transfer and through ONE ``features.resample`` launch (the same filter, csrc/resample.inc) before the STFT.
+
+Not here: log-mel features (``get_log_mel_spectrogram``: no recipe of the reference calls it).  ``edinburgh_tts_dataloader`` and
+``get_stft_from_subtraction`` are in data/edinburgh_tts.py and data/feature_utils.py."""
 import os
 
 import numpy as np
@@ -47,14 +51,39 @@ def _geometry(self, num_batch, feature_options, partition, device):
 
 
 def _eval_item(noisy, clean, window_size, hop_size, device):
-    """One whole recording in the evaluation contract (the STFT of the file as it is; only the reference is padded)."""
+    """One whole recording in the evaluation contract (the STFT of the file as it is; only the reference is padded).
+    ``noisy`` / ``clean``: host arrays, or 1-D tensors on the device."""
     from ..features import enhance_labels, stft_logmag
     n = min(len(noisy), len(clean))
-    wav = torch.from_numpy(np.ascontiguousarray(noisy[:n])[None]).to(device)
+    if torch.is_tensor(noisy):
+        wav = noisy[None, :n]
+        sig_ref = torch.nn.functional.pad(clean[:n], (0, 32 - n % 32))[None, None]
+    else:
+        wav = torch.from_numpy(np.ascontiguousarray(noisy[:n])[None]).to(device)
+        sig_ref = torch.from_numpy(np.pad(clean[:n], (0, 32 - n % 32))[None, None]).to(device)
     logmag, ri = stft_logmag(wav, window_size, hop_size)
     mag_noisy = enhance_labels(ri, None)[0]
-    sig_ref = torch.from_numpy(np.pad(clean[:n], (0, 32 - n % 32))[None, None]).to(device)
     return [logmag, mag_noisy], [ri[..., 0].contiguous(), ri[..., 1].contiguous(), sig_ref]
+
+
+def resampled_pair(f_a, f_b, sampling_rate, device):
+    """Two files' signals at ``sampling_rate`` as the rows of ONE device tensor, cut to the shorter one: (wav (2, n), n).  The
+    pair is uploaded as it is read, in one transfer, and converted by ONE ``features.resample`` launch (two when the files'
+    rates differ)."""
+    from ..features import resample
+    from .wsj0_2mix import read_wav
+    (a, rate_a), (b, rate_b) = read_wav(f_a), read_wav(f_b)
+    host = np.zeros((2, max(len(a), len(b))), np.float32)
+    host[0, :len(a)], host[1, :len(b)] = a, b
+    wav = torch.from_numpy(host).to(device)
+    if rate_a == rate_b:
+        y, _ = resample(wav, rate_a, sampling_rate, lengths=[len(a), len(b)])
+    else:
+        ya, yb = resample(wav[:1, :len(a)], rate_a, sampling_rate)[0], resample(wav[1:, :len(b)], rate_b, sampling_rate)[0]
+        n = min(ya.shape[1], yb.shape[1])
+        y = torch.cat([ya[:, :n], yb[:, :n]])
+    n = min(-(-len(a) * sampling_rate // rate_a), -(-len(b) * sampling_rate // rate_b))
+    return y[:, :n], n
 
 
 class DapsEnhanceFiles:
@@ -94,14 +123,18 @@ class DapsEnhanceFiles:
     def _open_next(self):
         """The next recording with at least one chunk in it: both signals through ONE STFT launch."""
         from ..features import stft_logmag
+        hip = options.get("loader_resample") == "hip"
         skipped = 0
         while True:
             if not self.pending:
                 order = self.rng.permutation(len(self.files)) if self.shuffle else np.arange(len(self.files))
                 self.pending = [self.files[i] for i in order]
             fn = self.pending.pop(0)
-            noisy, clean = self._signals(fn)
-            n = min(len(noisy), len(clean))
+            if hip:                    # the pair at its own rate in one transfer, one resample launch
+                wav, n = resampled_pair(*self.paths(fn), self.sampling_rate, self.device)
+            else:
+                noisy, clean = self._signals(fn)
+                n = min(len(noisy), len(clean))
             if 1 + n // self.hop_size >= self.frame_length and n > self.window_size // 2:
                 break
             skipped += 1
@@ -109,7 +142,8 @@ class DapsEnhanceFiles:
                 raise ValueError(f"daps_enhance_dataloader: no recording of {self.list_file!r} holds frame_length = "
                                  f"{self.frame_length} frames")
         self.opened.append(fn)
-        wav = torch.from_numpy(np.stack([noisy[:n], clean[:n]])).to(self.device)
+        if not hip:
+            wav = torch.from_numpy(np.stack([noisy[:n], clean[:n]])).to(self.device)
         logmag, ri = stft_logmag(wav, self.window_size, self.hop_size)
         self.cur, self.at = (logmag[0], ri[0], ri[1]), 0
 
@@ -123,7 +157,11 @@ class DapsEnhanceFiles:
 
     def _iter_eval(self):
         for fn in self.files:
-            yield _eval_item(*self._signals(fn), self.window_size, self.hop_size, self.device)
+            if options.get("loader_resample") == "hip":
+                wav, _ = resampled_pair(*self.paths(fn), self.sampling_rate, self.device)
+                yield _eval_item(wav[0], wav[1], self.window_size, self.hop_size, self.device)
+            else:
+                yield _eval_item(*self._signals(fn), self.window_size, self.hop_size, self.device)
 
     def __iter__(self):
         from ..features import enhance_labels

@@ -6,7 +6,9 @@ names, argument meaning and return types here (NumPy in, NumPy out), with the ar
 
     get_stft(fn, sampling_rate, window_size, hop_size) -> (T, F) complex64       feature_utils.py:5-21
         the file is read by ``read_wav`` (what ``librosa.load(fn, sr=None)`` returns for RIFF files), resampled when its rate
-        differs (``:17-20``), and goes through ONE ``stft_logmag`` launch (``onssen_stft_logmag_f32``: fp64 FFT in the LDS)
+        differs (``:17-20``; on the host, or on the device with option ``loader_resample = "hip"``), and goes through ONE ``stft_logmag`` launch (``onssen_stft_logmag_f32``: fp64 FFT in the LDS)
+    get_stft_from_subtraction(f_mix, f_clean, sampling_rate, window_size, hop_size) -> (T, F) complex64   feature_utils.py:24-33
+        the same for the difference of two files' signals (the noise of a noisy / clean pair), subtracted before resampling
     get_log_magnitude(stft, epsilon=1e-7) -> (T, F) float32                      feature_utils.py:49-51   onssen_log_magnitude_f32
     get_phase(stft) -> (T, F, 2) float32 (Re, Im)                                feature_utils.py:54-64   (a copy: no arithmetic)
     get_angle(stft) / get_cos_difference(stft_1, stft_2) -> (T, F) float32       feature_utils.py:67-80   onssen_cos_difference_f32
@@ -45,15 +47,54 @@ def _ri(stft, what):
     return torch.from_numpy(a.view(np.float32).reshape(-1)).to(_device()), a.shape
 
 
+def _signal(fn, sampling_rate, f_sub=None):
+    """The file's signal (minus ``f_sub``'s, when given) at ``sampling_rate`` as a (1, n) float32 device tensor.  A file at
+    another rate is resampled (feature_utils.py:17-20, :28-31) by ``scipy.signal.resample_poly`` on the host, or -- option
+    ``loader_resample = "hip"`` -- by the same filter on the device, the difference formed in fp64 on load."""
+    from .. import options
+    from ..features import resample
+    from .wsj0_2mix import _load, read_wav
+    if f_sub is None and options.get("loader_resample") != "hip":
+        return torch.from_numpy(_load(fn, int(sampling_rate))[None]).to(_device())
+    sig, rate = read_wav(fn)
+    sub = None
+    if f_sub is not None:
+        sub, rate_sub = read_wav(f_sub)
+        if rate_sub != rate:
+            raise ValueError(f"{fn} ({rate} Hz) and {f_sub} ({rate_sub} Hz) differ in sample rate")
+        n = min(len(sig), len(sub))
+        sig, sub = sig[:n], sub[:n]
+    if rate == int(sampling_rate) or options.get("loader_resample") != "hip":
+        if sub is not None:
+            sig = sig - sub                               # float32, as librosa.load's arrays subtract upstream
+        if rate != int(sampling_rate):
+            from math import gcd
+            from scipy.signal import resample_poly
+            g = gcd(rate, int(sampling_rate))
+            sig = resample_poly(sig, int(sampling_rate) // g, rate // g).astype(np.float32)
+        return torch.from_numpy(np.ascontiguousarray(sig)[None]).to(_device())
+    dev = _device()
+    pair = torch.from_numpy(np.stack([sig] if sub is None else [sig, sub])).to(dev)      # ONE transfer, at the file's own rate
+    return resample(pair[:1], rate, int(sampling_rate), sub=None if sub is None else pair[1:])[0]
+
+
+def _stft_of(wav, what, window_size, hop_size):
+    if wav.shape[1] <= window_size // 2:
+        raise ValueError(f"{what}: {wav.shape[1]} samples are too few for reflect padding of {window_size // 2}")
+    _, ri = stft_logmag(wav, int(window_size), int(hop_size))
+    return np.ascontiguousarray(ri[0].cpu().numpy()).view(np.complex64)[..., 0]
+
+
 def get_stft(fn, sampling_rate, window_size, hop_size):
     """fn: path of the wav file; returns the frame x frequency complex64 STFT (librosa < 0.10 defaults: periodic Hann window of
     ``window_size``, centred frames, reflect padding, 1 + n // hop_size frames)."""
-    from .wsj0_2mix import _load
-    sig = _load(fn, int(sampling_rate))
-    if sig.shape[0] <= window_size // 2:
-        raise ValueError(f"{fn}: {sig.shape[0]} samples are too few for reflect padding of {window_size // 2}")
-    _, ri = stft_logmag(torch.from_numpy(sig).to(_device()), int(window_size), int(hop_size))
-    return np.ascontiguousarray(ri[0].cpu().numpy()).view(np.complex64)[..., 0]
+    return _stft_of(_signal(fn, sampling_rate), fn, window_size, hop_size)
+
+
+def get_stft_from_subtraction(f_mix, f_clean, sampling_rate, window_size, hop_size):
+    """The STFT of ``f_mix``'s signal minus ``f_clean``'s -- the noise of a noisy / clean pair (feature_utils.py:24-33: the
+    difference is taken at the files' own rate and resampled afterwards).  Same result type as ``get_stft``."""
+    return _stft_of(_signal(f_mix, sampling_rate, f_clean), f_mix, window_size, hop_size)
 
 
 def get_log_magnitude(stft, epsilon=1e-7):
@@ -100,4 +141,4 @@ def get_one_hot(feature_mix, mag_s1, mag_s2, db_threshold):
     return out.cpu().numpy().astype(np.float64).reshape(f.shape + (2,))
 
 
-__all__ = ["get_stft", "get_log_magnitude", "get_phase", "get_angle", "get_cos_difference", "get_one_hot"]
+__all__ = ["get_stft", "get_stft_from_subtraction", "get_log_magnitude", "get_phase", "get_angle", "get_cos_difference", "get_one_hot"]

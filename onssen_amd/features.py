@@ -57,6 +57,55 @@ def stft_logmag(wav, window_size=256, hop_size=64, epsilon=1e-7, return_stft=Tru
     return logmag, ri
 
 
+_RESAMPLE_WS = {}      # (device, up, down) -> the ratio's phase-major tap image on that device
+
+
+def resample(wav, rate_in, rate_out, lengths=None, sub=None):
+    """wav (B, n) or (n,) float32 cuda tensor at ``rate_in`` -> (y (B, n_out) float32, lengths_out (B,) int32) at ``rate_out``:
+    ``scipy.signal.resample_poly(wav, rate_out / g, rate_in / g)`` (default window) in one launch, products and sums in fp64,
+    one rounding to fp32 (csrc/resample.inc).  n_out = ceil(n * rate_out / rate_in).
+
+    ``lengths`` (B,): a RAGGED batch -- row b holds lengths[b] <= n samples (nothing beyond them is read); its
+    lengths_out[b] = ceil(lengths[b] * rate_out / rate_in) outputs are bit for bit those of a batch-1 call on wav[b, :lengths[b]],
+    zeros follow them.  ``sub`` (same shape as wav): the filter's input is wav - sub, formed in fp64 on load
+    (``get_stft_from_subtraction``: the noise of a noisy / clean pair without a pass of its own).
+
+    The tap image of a ratio is built on its first use (one blocking copy) and kept per device: use a ratio once before
+    capturing it into a graph."""
+    if not wav.is_cuda or (sub is not None and not sub.is_cuda):
+        raise RuntimeError("resample: needs a tensor on a ROCm device; onssen_amd has no CPU fallback")
+    if wav.dim() == 1:
+        wav = wav[None]
+        sub = sub[None] if sub is not None and sub.dim() == 1 else sub
+    if sub is not None and sub.shape != wav.shape:
+        raise ValueError(f"resample: sub has shape {tuple(sub.shape)}, wav {tuple(wav.shape)}")
+    wav = wav.float()
+    if wav.stride(1) != 1 or wav.stride(0) < wav.shape[1]:
+        wav = wav.contiguous()
+    if sub is not None:
+        sub = sub.to(device=wav.device, dtype=torch.float32)
+        if sub.stride() != wav.stride():
+            wav, sub = wav.contiguous(), sub.contiguous()
+    B, n = wav.shape
+    lib, dev = get_lib(), wav.device
+    up, down, _, n_out = lib.resample_geometry(int(rate_in), int(rate_out), n)
+    ws = _RESAMPLE_WS.get((dev, up, down))
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"resample: the tap image of {rate_in} -> {rate_out} Hz is not built yet; call resample once before capturing")
+        ws = torch.empty(lib.resample_workspace_bytes(up, down) // 8, dtype=torch.float64, device=dev)
+        lib.resample_prepare(up, down, ws.data_ptr(), ws.numel() * 8, _stream())
+        _RESAMPLE_WS[(dev, up, down)] = ws
+    if lengths is not None:
+        lengths = _lengths_i32(lengths, B, n, dev, "lengths", lo=0)
+    y = torch.empty(B, n_out, device=dev, dtype=torch.float32)
+    lengths_out = torch.empty(B, device=dev, dtype=torch.int32)
+    lib.resample(wav.data_ptr(), sub.data_ptr() if sub is not None else None, wav.stride(0),
+                 lengths.data_ptr() if lengths is not None else None, B, n, up, down, y.data_ptr(), n_out, lengths_out.data_ptr(),
+                 ws.data_ptr(), ws.numel() * 8, _stream())
+    return y, lengths_out
+
+
 def mask_istft(stft_ri, masks, hop_size=64, length=None, frames=None, lengths=None):
     """stft_ri (B,T,F,2); masks (B,T,F,C) (any strides) or None ->
     (B, C, length) float32: istft(stft * mask_c) per speaker, librosa

@@ -103,6 +103,10 @@ TABLE = {
     "synthetic_data": ("ONSSEN_SYNTHETIC_DATA", "0", _flag, "wsj0_2mix_dataloader falls back to the synthetic corpus when data_path is empty"),
     "loader_workers": ("ONSSEN_LOADER_WORKERS", "4", _int, "file-reading threads of the wsj0-2mix file loader (0 = read on the calling thread)"),
     "loader_prefetch": ("ONSSEN_LOADER_PREFETCH", "3", _int, "batches the file loader keeps in flight ahead of the training step"),
+    "loader_resample": ("ONSSEN_LOADER_RESAMPLE", "scipy", _choice("scipy", "hip"),
+                        "a file whose rate differs from sampling_rate (feature_utils.get_stft / get_stft_from_subtraction, DapsEnhanceFiles): "
+                        "scipy = scipy.signal.resample_poly on the host (default), hip = the same filter on the device (features.resample); "
+                        "edinburgh_tts_dataloader always resamples on the device"),
     "world_size": ("WORLD_SIZE", "1", _int, "data-parallel ranks (torch.distributed.run exports it; a config may state it for checking)"),
 }
 
