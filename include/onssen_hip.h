@@ -699,6 +699,30 @@ int onssen_mask_istft_f32(const float* stft_ri, const float* mask, int64_t m_sb,
 int onssen_phase_istft_f32(const float* stft_ri, const float* mask, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf,
                            const float* phase, int64_t p_sc, int B, int C, int T, int n_fft, int hop, int length, float* out,
                            void* stream);
+/* onssen_phase_istft_f32 on a ragged batch: `frames` and `lengths` exactly as onssen_mask_istft_ragged_f32 below (frames[b] <= T
+ * frames in, lengths[b] <= length samples out, zeros after them); row b inside its own length is bit for bit the uniform call on
+ * that utterance alone (B = 1, T = frames[b]).  NULL `phase`, `frames` or `lengths`: ONSSEN_E_ARG. */
+int onssen_phase_istft_ragged_f32(const float* stft_ri, const float* mask, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf,
+                                  const float* phase, int64_t p_sc, int B, int C, int T, const int32_t* frames, int n_fft, int hop,
+                                  int length, const int32_t* lengths, float* out, void* stream);
+/* MISI (multiple input spectrogram inversion) half-step: from the mixture and C time-domain estimates to the C phase maps that
+ * the next onssen_phase_istft_f32 reads, in one launch.  Per sample, in fp64 on load,
+ *   d = (mix[n] - sum_{j<C} est_j[n]) / C  (sum in index order),   u_c[n] = est_c[n] + d
+ * -- the residual spread evenly, so that the estimates sum to the mixture; no waveform is written -- then Z_c = STFT(u_c) (centred
+ * frames, periodic Hann, reflect padding: the framing of onssen_stft_logmag_f32, fp64 transform) and
+ *   phase[c][b][t][f] = (Re Z_c / h, Im Z_c / h),  h = hypot(Re Z_c, Im Z_c) in fp64, rounded once to float32; (1, 0) where Z_c = 0.
+ *   mix    row b at mix + b*mix_stride, n_samples float32;  est (b, c) at est + b*est_sb + c*est_sc, unit sample stride
+ *   phase  (C, B, T, F, 2) float32, T = 1 + n_samples/hop, F = n_fft/2 + 1: onssen_phase_istft_f32's `phase` with p_sc = B*T*F*2
+ * Two speakers share one complex transform; deterministic, no atomics, no workspace.
+ * The ragged form: n_per_utt[b] samples of row b are valid (n_fft/2 < n_per_utt[b] <= n_max; a device value outside is clamped);
+ * the row mirrors about its own last sample, nothing beyond it is read, its frames 0 .. n_per_utt[b]/hop are bit for bit those of
+ * the uniform call on that row alone, and the frames after them, up to T = 1 + n_max/hop, are silence: (1, 0).
+ * Refused before anything is launched: a NULL pointer, B < 1, C < 2, C > 8, hop < 1, hop > n_fft, n_samples <= n_fft/2, n_fft not
+ * in {256, 512, 1024} (ONSSEN_E_ARG); `phase` not 8-byte aligned (ONSSEN_E_ALIGN: (re, im) pairs are stored as one word). */
+int onssen_misi_phase_f32(const float* mix, int64_t mix_stride, const float* est, int64_t est_sb, int64_t est_sc, int B, int C,
+                          int n_samples, int n_fft, int hop, float* phase, void* stream);
+int onssen_misi_phase_ragged_f32(const float* mix, int64_t mix_stride, const float* est, int64_t est_sb, int64_t est_sc, int B,
+                                 int C, int n_max, const int32_t* n_per_utt, int n_fft, int hop, float* phase, void* stream);
 /* The same from an estimated MAGNITUDE with the mixture's phase (enhancement's reconstruction): `mag` (strided like `mask`, not
  * NULL) and the spectrum at a bin is
  *   mag * X / |X|,  |X| = hypotf(Re X, Im X) and both quotients in float32, the product in fp64; (1, 0) for X / |X| where X = 0

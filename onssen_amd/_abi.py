@@ -132,6 +132,10 @@ SIGNATURES = {
     "onssen_dc_cluster_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _sz, _i, _vp]),
     "onssen_mask_istft_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "onssen_phase_istft_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "onssen_phase_istft_ragged_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    # MISI phase reconstruction: estimates -> phase maps of the next inverse transform
+    "onssen_misi_phase_f32": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
+    "onssen_misi_phase_ragged_f32": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "onssen_mag_istft_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "onssen_mag_istft_ragged_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     # deep-clustering separation without the embedding round trip (round 4)
@@ -627,9 +631,22 @@ class Lib:
         self.check(self.dll.onssen_mask_istft_f32(stft_ri, mask, m_sb, m_sc, m_st, m_sf, B, Cn, T, n_fft, hop,
                                                   length, out, stream), "onssen_mask_istft_f32")
 
-    def phase_istft(self, stft_ri, mask, m_sb, m_sc, m_st, m_sf, phase, p_sc, B, Cn, T, n_fft, hop, length, out, stream):
+    def phase_istft(self, stft_ri, mask, m_sb, m_sc, m_st, m_sf, phase, p_sc, B, Cn, T, n_fft, hop, length, out, stream, frames=None,
+                    lengths=None):
+        if frames is not None:       # ragged batch, as mask_istft
+            self.check(self.dll.onssen_phase_istft_ragged_f32(stft_ri, mask, m_sb, m_sc, m_st, m_sf, phase, p_sc, B, Cn, T, frames, n_fft,
+                                                              hop, length, lengths, out, stream), "onssen_phase_istft_ragged_f32")
+            return
         self.check(self.dll.onssen_phase_istft_f32(stft_ri, mask, m_sb, m_sc, m_st, m_sf, phase, p_sc, B, Cn, T, n_fft, hop,
                                                    length, out, stream), "onssen_phase_istft_f32")
+
+    def misi_phase(self, mix, mix_stride, est, est_sb, est_sc, B, Cn, n, n_fft, hop, phase, stream, n_per_utt=None):
+        if n_per_utt is not None:    # ragged batch: n = the longest row, n_per_utt[b] the valid samples of row b
+            self.check(self.dll.onssen_misi_phase_ragged_f32(mix, mix_stride, est, est_sb, est_sc, B, Cn, n, n_per_utt, n_fft, hop, phase,
+                                                             stream), "onssen_misi_phase_ragged_f32")
+            return
+        self.check(self.dll.onssen_misi_phase_f32(mix, mix_stride, est, est_sb, est_sc, B, Cn, n, n_fft, hop, phase, stream),
+                   "onssen_misi_phase_f32")
 
     def mag_istft(self, stft_ri, mag, m_sb, m_sc, m_st, m_sf, B, Cn, T, n_fft, hop, length, out, stream, frames=None, lengths=None):
         if frames is not None:       # ragged batch, as mask_istft

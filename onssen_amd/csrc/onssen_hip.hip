@@ -5,6 +5,8 @@
 //   fft.inc             stft_logmag_kernel (K1+K2: fp64 radix-4 FFT in LDS, one wavefront per PAIR of frames, fused log10(|X|+eps)),
 //                       mask_istft_kernel (K10: mask-apply + fp64 inverse FFT, two speakers per transform, gather overlap-add;
 //                       with its phase flag the operand is mask * |X| * the network's phase estimate: onssen_phase_istft_f32)
+//   misi.inc            misi_phase_kernel (MISI phase reconstruction: mixture + C estimates -> residual spread over the speakers, fp64
+//                       STFT of two speakers per transform, Z / |Z|: the phase maps of the next onssen_phase_istft_f32)
 //   gemm.inc            linear_x3q_kernel (K3/K7/K8/K9 on pre-split bf16 images: 256|128 x 320|256 tiles staged by LDS-DMA into a swizzled
 //                       layout, 8 waves, register epilogues), linear_x3p_kernel (round-1 form: 256x160 tiles; batched weight gradients;
 //                       bias | sigmoid | grouped L2-norm), linear_x3_kernel / linear_kernel (fp32-A forms, exact-fp32 MFMA),
@@ -129,6 +131,7 @@ static unsigned& xcd_spin_limit() {
 #include "lstm_bwd.inc"
 #include "lstm_run.inc"    // BLSTM host side: geometry, workspace layouts, launchers and the C ABI entries over lstm.inc / lstm_bwd.inc
 #include "fft.inc"
+#include "misi.inc"       // MISI phase reconstruction: the half-step between two inverse transforms (estimates -> phase maps)
 #include "loss_sdr.inc"
 #include "wav_io.inc"      // host code: the batch RIFF reader of the file loader
 #include "optim.inc"
@@ -873,6 +876,25 @@ int onssen_phase_istft_f32(const float* stft_ri, const float* mask, int64_t m_sb
   if (!phase) return ONSSEN_E_ARG;
   return mask_istft_impl(stft_ri, mask, m_sb, m_sc, m_st, m_sf, B, C, T, n_fft, hop, length, out, stream, nullptr, nullptr, phase,
                          p_sc);
+}
+
+int onssen_phase_istft_ragged_f32(const float* stft_ri, const float* mask, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf,
+                                  const float* phase, int64_t p_sc, int B, int C, int T, const int32_t* frames, int n_fft, int hop,
+                                  int length, const int32_t* lengths, float* out, void* stream) {
+  if (!phase || !frames || !lengths) return ONSSEN_E_ARG;
+  return mask_istft_impl(stft_ri, mask, m_sb, m_sc, m_st, m_sf, B, C, T, n_fft, hop, length, out, stream, frames, lengths, phase,
+                         p_sc);
+}
+
+int onssen_misi_phase_f32(const float* mix, int64_t mix_stride, const float* est, int64_t est_sb, int64_t est_sc, int B, int C,
+                          int n_samples, int n_fft, int hop, float* phase, void* stream) {
+  return misi_phase_impl(mix, mix_stride, est, est_sb, est_sc, B, C, n_samples, n_fft, hop, phase, stream, nullptr);
+}
+
+int onssen_misi_phase_ragged_f32(const float* mix, int64_t mix_stride, const float* est, int64_t est_sb, int64_t est_sc, int B,
+                                 int C, int n_max, const int32_t* n_per_utt, int n_fft, int hop, float* phase, void* stream) {
+  if (!n_per_utt) return ONSSEN_E_ARG;
+  return misi_phase_impl(mix, mix_stride, est, est_sb, est_sc, B, C, n_max, n_fft, hop, phase, stream, n_per_utt);
 }
 
 int onssen_mag_istft_f32(const float* stft_ri, const float* mag, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf, int B,

@@ -283,36 +283,48 @@ class tester_dc(tester):
         return mask_istft(ri, masks, self.hop_size, sig_ref.shape[-1], frames=frames, lengths=lengths), sig_ref.float()
 
 
-class tester_chimera(tester):
-    """egs/wsj0-2mix/chimera/evaluate.py:23-45: the network's masks, mask-apply + iSTFT."""
+def _misi_est(ri, masks, hop_size, n, iters, frames, lengths):
+    """Estimates of a mask tester: ``mask_istft``, or ``iters`` MISI iterations after it.  The testers hold the mixture only as
+    a spectrum; MISI's waveform is its inverse transform with the same ``frames`` and ``lengths`` (one launch)."""
+    from .features import mask_istft
+    if not iters:
+        return mask_istft(ri, masks, hop_size, n, frames=frames, lengths=lengths)
+    from .separation import misi
+    wav = mask_istft(ri, None, hop_size, n, frames=frames, lengths=lengths)[:, 0]
+    return misi(ri, masks, wav, iters, hop_size, frames=frames, lengths=lengths)
 
-    def __init__(self, args, hop_size=64):
+
+class tester_chimera(tester):
+    """egs/wsj0-2mix/chimera/evaluate.py:23-45: the network's masks, mask-apply + iSTFT.  ``misi_iters`` = K > 0 (extension):
+    K iterations of MISI phase reconstruction after the masks (``separation.misi``)."""
+
+    def __init__(self, args, hop_size=64, misi_iters=0):
+        from .separation import _misi_iters
         super().__init__(args)
-        self.hop_size = hop_size
+        self.hop_size, self.misi_iters = hop_size, _misi_iters(misi_iters, "tester_chimera")
 
     def get_est_sig(self, input, label, output, frames=None, lengths=None):
-        from .features import mask_istft
         _, mask_A, mask_B = output
         ri, sig_ref = _mix_ri(label)
         masks = torch.stack([mask_A, mask_B], -1)
-        return mask_istft(ri, masks, self.hop_size, sig_ref.shape[-1], frames=frames, lengths=lengths), sig_ref.float()
+        return _misi_est(ri, masks, self.hop_size, sig_ref.shape[-1], self.misi_iters, frames, lengths), sig_ref.float()
 
 
 class tester_upit(tester):
     """The uPIT mask network (upstream has no evaluation for it) on the evaluation loader: the item is the chimera one with
     ``sig_ref (B,S,n)``, S = 2 .. 4; the network's S masks, mask-apply + iSTFT.  ``eval(batch=K)`` is the base class's ragged
-    loop."""
+    loop.  ``misi_iters`` = K > 0: K iterations of MISI phase reconstruction after the masks (``separation.misi``)."""
 
-    def __init__(self, args, hop_size=64):
+    def __init__(self, args, hop_size=64, misi_iters=0):
+        from .separation import _misi_iters
         super().__init__(args)
-        self.hop_size = hop_size
+        self.hop_size, self.misi_iters = hop_size, _misi_iters(misi_iters, "tester_upit")
 
     def get_est_sig(self, input, label, output, frames=None, lengths=None):
-        from .features import mask_istft
         from .loss import _upit_masks_base
         ri, sig_ref = _mix_ri(label)
         masks = _upit_masks_base(list(output))            # the network's (B,T,F,S) buffer when the masks are its planes
-        return mask_istft(ri, masks, self.hop_size, sig_ref.shape[-1], frames=frames, lengths=lengths), sig_ref.float()
+        return _misi_est(ri, masks, self.hop_size, sig_ref.shape[-1], self.misi_iters, frames, lengths), sig_ref.float()
 
 
 class tester_phase(tester):

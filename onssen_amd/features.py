@@ -141,13 +141,18 @@ def mask_istft(stft_ri, masks, hop_size=64, length=None, frames=None, lengths=No
     return out
 
 
-def phase_istft(stft_ri, masks, phases, hop_size=64, length=None):
+def phase_istft(stft_ri, masks, phases, hop_size=64, length=None, frames=None, lengths=None, out=None):
     """stft_ri (B,T,F,2); masks (B,T,F,C) (any strides); phases: C tensors (B,T,F,2), or one (C,B,T,F,2) ->
     (B, C, length) float32: istft(mask_c * |stft| * (phase_c.re + i phase_c.im)) per speaker -- phase_net's reconstruction from
-    its masks and unit phase vectors (mask_istft re-uses the mixture's phase instead).  Uniform batches only.
+    its masks and unit phase vectors (mask_istft re-uses the mixture's phase instead).
 
     The phase maps are read where they are when they lie at one common distance from each other (two slices of one buffer,
-    as phase_net's forward returns them; any two fp32 tensors); otherwise they are stacked first."""
+    as phase_net's forward returns them; any two fp32 tensors); otherwise they are stacked first.
+
+    ``frames`` / ``lengths`` (B,): a RAGGED batch exactly as in ``mask_istft`` (both or neither).  ``out``: a (B, C, length)
+    float32 contiguous tensor to write into instead of a new one (``separation.misi`` re-uses one across its iterations)."""
+    if (frames is None) != (lengths is None):
+        raise ValueError("phase_istft: a ragged batch needs both frames= and lengths=")
     if not stft_ri.is_cuda:
         raise RuntimeError("phase_istft: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
     stft_ri = stft_ri.float().contiguous()
@@ -155,6 +160,11 @@ def phase_istft(stft_ri, masks, phases, hop_size=64, length=None):
     n_fft = 2 * (F - 1)
     if length is None:
         length = hop_size * (T - 1)
+    rag = {}
+    if frames is not None:
+        frames = _lengths_i32(frames, B, T, stft_ri.device, "frames")
+        lengths = _lengths_i32(lengths, B, length, stft_ri.device, "lengths")
+        rag = dict(frames=frames.data_ptr(), lengths=lengths.data_ptr())
     masks = masks.float()
     C = masks.shape[3]
     phases = [p.float().contiguous() for p in (phases.unbind(0) if torch.is_tensor(phases) else phases)]
@@ -165,10 +175,47 @@ def phase_istft(stft_ri, masks, phases, hop_size=64, length=None):
         stacked = torch.stack(phases)                    # kept alive until the launch below is queued
         phases = list(stacked.unbind(0))
         step = {phases[1].data_ptr() - phases[0].data_ptr()}
-    out = torch.empty(B, C, length, device=stft_ri.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(B, C, length, device=stft_ri.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, C, length) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != stft_ri.device:
+        raise ValueError(f"phase_istft: out must be a contiguous float32 tensor of shape {(B, C, length)} on {stft_ri.device}")
     get_lib().phase_istft(stft_ri.data_ptr(), masks.data_ptr(), masks.stride(0), masks.stride(3), masks.stride(1), masks.stride(2),
                           phases[0].data_ptr(), step.pop() // 4 if step else 0, B, C, T, n_fft, hop_size, length, out.data_ptr(),
-                          _stream())
+                          _stream(), **rag)
+    return out
+
+
+def misi_phase(mix, est, window_size=256, hop_size=64, lengths=None, out=None):
+    """The half-step of MISI (multiple input spectrogram inversion) between two inverse transforms, one launch (csrc/misi.inc):
+    mix (B, n), est (B, C, n) float32 cuda tensors, 2 <= C <= 8 -> (C, B, T, F, 2) float32 unit phase vectors, T = 1 + n // hop,
+    F = window_size // 2 + 1 -- what ``phase_istft`` takes as ``phases``.  Per sample, in fp64, the mixture's residual is spread
+    evenly over the speakers, u_c = est_c + (mix - sum_j est_j) / C, and the phase of STFT(u_c) (the framing of ``stft_logmag``)
+    is kept: Z / |Z|, (1, 0) where Z = 0.  ``est`` is read where it is with any batch and speaker strides (unit sample stride).
+
+    ``lengths`` (B,): a RAGGED batch as in ``stft_logmag`` -- nothing beyond lengths[b] is read, row b's own 1 + lengths[b] // hop
+    frames are bit for bit those of a batch-1 call, the frames after them are silence, (1, 0).  ``out``: a (C, B, T, F, 2) float32
+    contiguous tensor to write into instead of a new one."""
+    if not mix.is_cuda or not est.is_cuda:
+        raise RuntimeError("misi_phase: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
+    if mix.dim() != 2 or est.dim() != 3 or est.shape[0] != mix.shape[0] or est.shape[2] != mix.shape[1]:
+        raise ValueError(f"misi_phase: expected mix (B, n) and est (B, C, n), got {tuple(mix.shape)} and {tuple(est.shape)}")
+    mix, est = mix.float(), est.float()
+    if mix.stride(1) != 1:
+        mix = mix.contiguous()
+    if est.stride(2) != 1:
+        est = est.contiguous()
+    B, C, n = est.shape
+    if not 2 <= C <= 8:
+        raise ValueError(f"misi_phase: {C} speakers; the kernel takes 2 .. 8")
+    T, F = 1 + n // hop_size, window_size // 2 + 1
+    if lengths is not None:      # (every utterance must be longer than window_size / 2 samples: reflect padding)
+        lengths = _lengths_i32(lengths, B, n, mix.device, "lengths", lo=window_size // 2 + 1)
+    if out is None:
+        out = torch.empty(C, B, T, F, 2, device=mix.device, dtype=torch.float32)
+    elif tuple(out.shape) != (C, B, T, F, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != mix.device:
+        raise ValueError(f"misi_phase: out must be a contiguous float32 tensor of shape {(C, B, T, F, 2)} on {mix.device}")
+    get_lib().misi_phase(mix.data_ptr(), mix.stride(0), est.data_ptr(), est.stride(0), est.stride(1), B, C, n, window_size, hop_size,
+                         out.data_ptr(), _stream(), n_per_utt=lengths.data_ptr() if lengths is not None else None)
     return out
 
 

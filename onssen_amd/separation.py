@@ -20,46 +20,108 @@ def _ragged(wav, lengths, hop_size):
     return lengths, (1 + lengths // hop_size).to(torch.int32)
 
 
+def _misi_iters(iters, who):
+    """``iters`` as a non-negative int, or ValueError."""
+    import numbers
+    if isinstance(iters, bool) or not isinstance(iters, numbers.Integral) or iters < 0:
+        raise ValueError(f"{who}: the number of MISI iterations must be a non-negative integer, got {iters!r}")
+    return int(iters)
+
+
+@torch.no_grad()
+def misi(stft_ri, masks, wav, iters, hop_size=64, frames=None, lengths=None, phases=None):
+    """MISI (multiple input spectrogram inversion: Gunawan & Sen 2010; the phase reconstruction of Wang, Le Roux, Wang & Hershey
+    2018 after a chimera++ network) on the device: stft_ri (B,T,F,2) the mixture's spectrum, masks (B,T,F,C) (any strides), wav
+    (B, n) the mixture -> (B, C, n) float32.  The estimated magnitudes mask_c |X| stay fixed; the phases start as the mixture's
+    (``mask_istft``) -- or as ``phases``, C maps (B,T,F,2) of unit vectors such as phase_net's, through ``phase_istft`` -- and every
+    iteration is two launches: ``features.misi_phase`` (the residual mix - sum of the estimates spread evenly over the speakers,
+    STFT, Z / |Z|: csrc/misi.inc) and ``features.phase_istft`` with those phases.
+
+    ``iters`` = 0 returns exactly ``mask_istft(...)`` (``phase_istft(...)`` with ``phases``) and launches nothing else.  ``frames``
+    / ``lengths`` (B,): a ragged batch as in ``mask_istft`` (both or neither).  Nothing is read back by the host and the
+    phase buffer and the estimates are allocated once per call, so a call can be captured in a hipGraph."""
+    from .features import misi_phase, phase_istft
+    iters = _misi_iters(iters, "misi")
+    if (frames is None) != (lengths is None):
+        raise ValueError("misi: a ragged batch needs both frames= and lengths=")
+    if not stft_ri.is_cuda or not wav.is_cuda:
+        raise RuntimeError("misi: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
+    if wav.dim() == 1:
+        wav = wav[None]
+    n = wav.shape[-1]
+    if phases is not None:
+        est = phase_istft(stft_ri, masks, phases, hop_size, n, frames=frames, lengths=lengths)
+    else:
+        est = mask_istft(stft_ri, masks, hop_size, n, frames=frames, lengths=lengths)
+    if iters == 0:
+        return est
+    if frames is not None:       # validated once, passed on as device tensors
+        from .features import _lengths_i32
+        frames = _lengths_i32(frames, est.shape[0], stft_ri.shape[1], est.device, "frames")
+        lengths = _lengths_i32(lengths, est.shape[0], n, est.device, "lengths")
+    stft_ri, masks = stft_ri.float().contiguous(), masks.float()
+    n_fft = 2 * (stft_ri.shape[2] - 1)
+    ph = None
+    for _ in range(iters):
+        ph = misi_phase(wav, est, n_fft, hop_size, lengths=lengths, out=ph)
+        est = phase_istft(stft_ri, masks, ph, hop_size, n, frames=frames, lengths=lengths, out=est)
+    return est
+
+
 @recovering
 @torch.no_grad()
-def separate_chimera(model, wav, window_size=256, hop_size=64, lengths=None):
+def separate_chimera(model, wav, window_size=256, hop_size=64, lengths=None, misi_iters=0):
     """wav (B, n) cuda float32 -> (B, 2, n): masks straight from the network.  ``lengths`` (B,): a ragged batch of whole
-    utterances padded to n samples (see separate_dc)."""
+    utterances padded to n samples (see separate_dc).  ``misi_iters`` = K > 0: K iterations of MISI phase reconstruction after
+    the masks (``misi``; two launches each); 0 is the mixture's phase, the reference's result."""
+    misi_iters = _misi_iters(misi_iters, "separate_chimera")
     lengths, frames = _ragged(wav, lengths, hop_size)
     logmag, ri = stft_logmag(wav, window_size, hop_size, lengths=lengths)
     _, masks = model.embedding_and_masks(logmag, frames)
-    out = mask_istft(ri, masks, hop_size, wav.shape[-1], frames=frames, lengths=lengths)
+    if misi_iters:
+        out = misi(ri, masks, wav, misi_iters, hop_size, frames=frames, lengths=lengths)
+    else:
+        out = mask_istft(ri, masks, hop_size, wav.shape[-1], frames=frames, lengths=lengths)
     _XcdStatus.flush()            # an aborted recurrence is caught HERE (and the call re-run, see `recovering`), not by the next call
     return out
 
 
 @recovering
 @torch.no_grad()
-def separate_upit(model, wav, window_size=256, hop_size=64, lengths=None):
+def separate_upit(model, wav, window_size=256, hop_size=64, lengths=None, misi_iters=0):
     """wav (B, n) cuda float32 -> (B, S, n), S = ``model.num_speaker`` (2 .. 4): STFT -> ``uPIT_LSTM.masks`` -> ``mask_istft``.
     Nothing is read back by the host, so a call can be captured in a hipGraph.  ``lengths`` (B,): a ragged batch of whole
     utterances padded to n samples; every row inside its own length is bit for bit its batch-1 result, zeros after it (see
-    separate_dc)."""
+    separate_dc).  ``misi_iters`` = K > 0: K iterations of MISI phase reconstruction after the masks (``misi``)."""
+    misi_iters = _misi_iters(misi_iters, "separate_upit")
     lengths, frames = _ragged(wav, lengths, hop_size)
     logmag, ri = stft_logmag(wav, window_size, hop_size, lengths=lengths)
     masks = model.masks(logmag, frames)
-    out = mask_istft(ri, masks, hop_size, wav.shape[-1], frames=frames, lengths=lengths)
+    if misi_iters:
+        out = misi(ri, masks, wav, misi_iters, hop_size, frames=frames, lengths=lengths)
+    else:
+        out = mask_istft(ri, masks, hop_size, wav.shape[-1], frames=frames, lengths=lengths)
     _XcdStatus.flush()            # an aborted recurrence is caught HERE (and the call re-run, see `recovering`), not by the next call
     return out
 
 
 @recovering
 @torch.no_grad()
-def separate_phase(model, wav, window_size=256, hop_size=64):
+def separate_phase(model, wav, window_size=256, hop_size=64, misi_iters=0):
     """wav (B, n) cuda float32 -> (B, 2, n): phase_net's masks AND its phase estimates go into the inverse transform
-    (features.phase_istft); the mixture's phase is only the network's input.  Uniform batches (phase_net has no ragged forward)."""
+    (features.phase_istft); the mixture's phase is only the network's input.  Uniform batches (phase_net has no ragged forward).
+    ``misi_iters`` = K > 0: K iterations of MISI after that, starting from the network's phases (``misi(..., phases=)``)."""
     from .features import phase_istft
+    misi_iters = _misi_iters(misi_iters, "separate_phase")
     logmag, ri = stft_logmag(wav, window_size, hop_size)
     _, mask_A, mask_B, phase_A, phase_B = model([logmag, ri])
     base = getattr(mask_A, "_base", None)            # the network's (B,T,F,2) mask buffer, when both masks are its planes
     if base is None or getattr(mask_B, "_base", None) is not base or base.shape != mask_A.shape + (2,):
         base = torch.stack([mask_A, mask_B], -1)
-    out = phase_istft(ri, base, [phase_A, phase_B], hop_size, wav.shape[-1])
+    if misi_iters:
+        out = misi(ri, base, wav, misi_iters, hop_size, phases=[phase_A, phase_B])
+    else:
+        out = phase_istft(ri, base, [phase_A, phase_B], hop_size, wav.shape[-1])
     _XcdStatus.flush()            # an aborted recurrence is caught HERE (and the call re-run, see `recovering`), not by the next call
     return out
 
