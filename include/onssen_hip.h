@@ -346,6 +346,16 @@ int onssen_blstm_pipe2_y_image(int B, int T, int in_dim, int H, int ug, size_t* 
 int onssen_blstm_pipe2_forward_f32(const float* x, int64_t xs_b, int64_t xs_t, int B, int T, int in_dim, int H, int ug,
                                    const float* const* wih_p_host, const float* const* whh_p_host,
                                    const float* const* bias_p_host, void* ws, size_t ws_bytes, int flags, void* stream);
+/* ... that ALSO builds the deep-clustering target map of batch n (x is its log-magnitude, dense [B][T][in_dim]: xs_t = in_dim,
+ * xs_b = T * in_dim): what onssen_dc_index_f32(x, B, T, NULL, in_dim, D, db_threshold, map_ws, map_ws_bytes) leaves in map_ws, byte
+ * for byte, built by min(16, B) extra workgroups at the end of the persistent launch's grid -- on the CUs its members leave free --
+ * instead of three launches in front of it.  map_ws is validated as onssen_dc_index_f32 validates its workspace; everything else
+ * is onssen_blstm_pipe2_forward_f32 (ONSSEN_BLSTM_G_READY included: the launch alone still builds the map).  The map is complete
+ * when the call's launches are, whether or not the recurrence gave up a wait. */
+int onssen_blstm_pipe2_map_forward_f32(const float* x, int64_t xs_b, int64_t xs_t, int B, int T, int in_dim, int H, int ug,
+                                       const float* const* wih_p_host, const float* const* whh_p_host,
+                                       const float* const* bias_p_host, void* ws, size_t ws_bytes, int flags, float db_threshold, int D,
+                                       void* map_ws, size_t map_ws_bytes, void* stream);
 /* ... over a stream of RAGGED batches of whole utterances (round 6c; the reference evaluates them one by one, onssen/utils/test.py:29-41;
  * onssen_blstm_forward_ragged_f32 runs K of different lengths per call): batch n is B <= 16 rows padded to ITS longest utterance,
  * T frames, row b live for frames[b] <= T of them; the launch's other half still works on batch n-1 (T_prev, frames_prev -- the

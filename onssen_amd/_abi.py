@@ -61,6 +61,7 @@ SIGNATURES = {
     "onssen_blstm_pipe2_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "onssen_blstm_pipe2_y_image": (_i, [_i, _i, _i, _i, _i, _vp, _vp]),
     "onssen_blstm_pipe2_forward_f32": (_i, [_vp, _i64, _i64, _i, _i, _i, _i, _i, _pp, _pp, _pp, _vp, _sz, _i, _vp]),
+    "onssen_blstm_pipe2_map_forward_f32": (_i, [_vp, _i64, _i64, _i, _i, _i, _i, _i, _pp, _pp, _pp, _vp, _sz, _i, _f, _i, _vp, _sz, _vp]),
     "onssen_blstm_pipe2_forward_ragged_f32": (_i, [_vp, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _pp, _pp, _pp, _vp, _sz, _i, _vp]),
     "onssen_linear_x3p_batched": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp, _i, _vp, _i64, _i64, _i, _vp]),
     "onssen_linear_x3p_batched_split": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _i64, _i, _vp, _i64, _i64, _i64,
@@ -516,6 +517,14 @@ class Lib:
         self.check(self.dll.onssen_blstm_pipe2_forward_f32(x, xs_b, xs_t, B, T, in_dim, H, ug, arr(*wih_ptrs), arr(*whh_ptrs),
                                                            arr(*bias_ptrs), ws, ws_bytes, flags, stream),
                    "onssen_blstm_pipe2_forward_f32")
+
+    def blstm_pipe2_map_forward(self, x, xs_b, xs_t, B, T, in_dim, H, ug, wih_ptrs, whh_ptrs, bias_ptrs, ws, ws_bytes, flags, db, D,
+                                map_ws, map_ws_bytes, stream):
+        """``blstm_pipe2_forward`` whose persistent launch also builds the target map of x (``dc_index``'s bytes) in ``map_ws``."""
+        arr = C.c_void_p * 2
+        self.check(self.dll.onssen_blstm_pipe2_map_forward_f32(x, xs_b, xs_t, B, T, in_dim, H, ug, arr(*wih_ptrs), arr(*whh_ptrs),
+                                                               arr(*bias_ptrs), ws, ws_bytes, flags, db, D, map_ws, map_ws_bytes, stream),
+                   "onssen_blstm_pipe2_map_forward_f32")
 
     def blstm_pipe2_forward_ragged(self, x, xs_b, xs_t, B, T_cap, T, frames, T_prev, frames_prev, in_dim, H, ug, wih_ptrs, whh_ptrs,
                                    bias_ptrs, ws, ws_bytes, flags, stream):

@@ -914,6 +914,123 @@ __global__ __launch_bounds__(256) void kmeans2_index_kernel(const float* __restr
   }
 }
 
+// argmax of bins [lo, hi) of f by one workgroup of NTHR threads: (-inf, none) if there is none, ties to the smallest index (rv, ri:
+// NTHR words of LDS each, free again on return)
+template <int NTHR>
+__device__ __forceinline__ void kmeans2_block_argmax(const float* __restrict__ f, long lo, long hi, int none, float* rv, int* ri,
+                                                     float& v, int& ix) {
+  const int tid = threadIdx.x;
+  float best = -INFINITY;
+  int bi = none;
+#pragma unroll 8
+  for (long i = lo + tid; i < hi; i += NTHR)
+    if (f[i] > best) { best = f[i]; bi = (int)i; }
+  rv[tid] = best; ri[tid] = bi;
+  __syncthreads();
+  for (int s = NTHR / 2; s > 0; s >>= 1) {
+    if (tid < s && (rv[tid + s] > rv[tid] || (rv[tid + s] == rv[tid] && ri[tid + s] < ri[tid]))) { rv[tid] = rv[tid + s]; ri[tid] = ri[tid + s]; }
+    __syncthreads();
+  }
+  v = rv[0]; ix = ri[0];
+  __syncthreads();
+}
+
+// The target map of WHOLE utterances by one workgroup of NTHR threads: what kmeans2_search_kernel<0>, kmeans2_count_kernel<true> and
+// kmeans2_index_kernel leave for a uniform batch, word for word, for the utterances first, first + step, ... < B.  Called by the spare
+// workgroups of the pair launch (lstm_xcd_kernel<AUX>), which lend it `lds` (NTHR * 8 + 512 bytes).  Nothing crosses workgroups, so the
+// NBLK partials and chunk bases collapse: the argmax is taken over the utterance at once (same order: larger value, then smaller
+// index), dest[i] is the number of active bins before bin i (what chunk base + in-block scan add up to), and a chunk's count is the
+// difference of that number at its two ends.  Integers and one float compare per bin: the same bits whatever the partition.
+template <int NTHR>
+__device__ __forceinline__ void kmeans2_map_workgroup(const float* __restrict__ feat, long per_utt, float db, float* __restrict__ ws, long ws_stride,
+                                      int* __restrict__ iw, int* __restrict__ dest, int D, int B, int first, int step, char* lds) {
+  using namespace km;
+  static_assert(NBLK == 64 && IW == 72, "the int words of an utterance: 64 chunk counts, then 8 counters");
+  constexpr int NWV = NTHR / 64, RUN = 8;            // a thread scans RUN consecutive bins of a tile of NTHR * RUN
+  float* rv = reinterpret_cast<float*>(lds);         // [NTHR] argmax values ...
+  int* ri = reinterpret_cast<int*>(rv + NTHR);       // [NTHR] ... and indices
+  int* wtot = ri + NTHR;                             // [2][NWV] active bins per wave of a tile (two tiles in flight)
+  int* cs = wtot + 2 * NWV;                          // [NBLK] active bins before each chunk
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int nb = (int)per_utt;                       // (per_utt < 2^31, as everywhere here)
+  const int chunk = (nb + NBLK - 1) / NBLK;
+  const int ntag = 2 * NBP * (D + 4);
+  for (int b = first; b < B; b += step) {
+    const float* f = feat + (long)b * per_utt;
+    float* w = ws + (long)b * ws_stride;
+    float* part = w + 1 + 2 * D;
+    int* iwb = iw + (long)b * IW;
+    int* dst = dest + (long)b * per_utt;
+    float vmax;
+    int imax;
+    kmeans2_block_argmax<NTHR>(f, 0, nb, nb, rv, ri, vmax, imax);
+    const float thr = vmax - db / 20.0f;
+    int base = 0, par = 0;                           // active bins before this tile; which half of wtot it uses
+    for (long t0 = 0; t0 < nb; t0 += (long)NTHR * RUN, par ^= 1) {
+      const long i0 = t0 + (long)tid * RUN;
+      int act[RUN], c = 0;
+#pragma unroll
+      for (int r = 0; r < RUN; ++r) {
+        act[r] = (i0 + r < nb && f[i0 + r] >= thr) ? 1 : 0;
+        c += act[r];
+      }
+      int incl = c;                                  // inclusive scan over the wave, then the waves before this one
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int v = __builtin_bit_cast(int, __shfl(__builtin_bit_cast(float, incl), (lane - o) & 63));      // (a bit move)
+        if (lane >= o) incl += v;
+      }
+      if (lane == 63) wtot[par * NWV + wv] = incl;
+      __syncthreads();
+      int pos = base + incl - c;
+#pragma unroll
+      for (int k = 0; k < NWV; ++k) {
+        const int t = wtot[par * NWV + k];
+        if (k < wv) pos += t;
+        base += t;
+      }
+      if (i0 < nb) {
+        unsigned kc = ((unsigned)i0 + (unsigned)chunk - 1u) / (unsigned)chunk;      // the first chunk that starts at or after i0
+        long cstart = (long)kc * chunk;
+#pragma unroll
+        for (int r = 0; r < RUN; ++r) {
+          const long i = i0 + r;
+          if (i < nb) {
+            if (i == cstart) { cs[kc] = pos; ++kc; cstart += chunk; }
+            dst[i] = act[r] ? pos : -1;
+            pos += act[r];
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < NBLK) {                                // chunks past the last bin start (and end) at the total
+      const int c_lo = (long)tid * chunk < nb ? cs[tid] : base;
+      const int c_hi = (tid + 1 < NBLK && (long)(tid + 1) * chunk < nb) ? cs[tid + 1] : base;
+      iwb[tid] = c_hi - c_lo;
+    }
+    if (tid < 8) iwb[64 + tid] = tid == 0 ? base : 0;     // n_active, fresh counters
+    if (tid == 0) {
+      w[0] = vmax;
+      w[ws_stride - 1] = __builtin_bit_cast(float, imax);
+    }
+    // the Lloyd kernel's tagged words cover the scratch of the searches up to word ntag; the partials of the chunks behind that
+    // (a narrow embedding only: ntag >= 2 NBLK from D = 4 on) stay as the search leaves them
+    for (int k = tid; k < ntag; k += NTHR) part[k] = __builtin_bit_cast(float, 1u);
+    for (int k = ntag / 2; k < NBLK; ++k) {
+      const long lo = (long)k * chunk, hi = lo + chunk < nb ? lo + chunk : nb;
+      float v;
+      int ix;
+      kmeans2_block_argmax<NTHR>(f, lo, hi, nb, rv, ri, v, ix);
+      if (tid == 0) {
+        part[2 * k] = v;
+        part[2 * k + 1] = __builtin_bit_cast(float, ix);
+      }
+    }
+    __syncthreads();                                 // cs and wtot are the next utterance's
+  }
+}
+
 // masks of the compacted form: bin i is labelled from row dest[i] of the compacted array (the arithmetic of
 // kmeans2_assign_kernel<1>: same distances, same labels), silent bins get (0, 0)
 template <int DT>

@@ -450,6 +450,16 @@ struct XcdArgs {
   // whole utterances, each padded to its own longest one -- the second recurrence runs T_b time steps over rows of frames_b[b] frames
   int T_b = 0;                            // RAGGED: time steps of the second recurrence (a uniform pair runs T in both)
   const int* frames_b = nullptr;          // RAGGED: [B] frames of the second recurrence's rows
+  // AUX workgroups (onssen_blstm_pipe2_map_forward_f32): the aux_n workgroups behind the 8 NU members build the target map of the
+  // second recurrence's batch (kmeans2_map_workgroup, labels_cluster.inc) on the CUs the members leave free; they share nothing with
+  // the recurrences but the launch.  aux_n = 0: an ordinary launch
+  int aux_n = 0, aux_D = 0;
+  float aux_db = 0.f;
+  const float* aux_feat = nullptr;        // [B][aux_per_utt] log-magnitude
+  long aux_per_utt = 0, aux_stride = 0;   // bins per utterance; floats per utterance of the clustering workspace's header
+  float* aux_w = nullptr;                 // clustering workspace: header ...
+  int* aux_iw = nullptr;                  // ... int words ...
+  int* aux_dest = nullptr;                // ... target map
 };
 
 // broadcast lane J of every lane quad (DPP quad_perm, one VALU op; all four lanes of a quad must be active)
@@ -469,9 +479,12 @@ __device__ __forceinline__ unsigned quad_bcast(unsigned v) {
 // direction then starts from zero state at the row's own last frame, the forward direction stops there -- so every row's
 // outputs at its own frames are what a batch-1 run of that utterance gives, bit for bit (a tile column never sees its
 // neighbours).  A template flag: one compare and two selects per element and step that the other instantiations do not carry.
-template <int NT, int NW, bool FUSE, int TERMS, bool STACK, bool SAVE = false, bool RAGGED = false>
+// AUX (the uniform pair launch of onssen_blstm_pipe2_map_forward_f32 only): the workgroups behind the 8 NU members build a target map
+// and return -- a template flag, so that no other instantiation carries the branch.
+template <int NT, int NW, bool FUSE, int TERMS, bool STACK, bool SAVE = false, bool RAGGED = false, bool AUX = false>
 __global__ __launch_bounds__(64 * NW) void lstm_xcd_kernel(XcdArgs p) {
   static_assert(!STACK || TERMS == 3, "stacking is a property of the split form");
+  static_assert(!AUX || (TERMS == 3 && !FUSE && !SAVE && !RAGGED), "aux workgroups ride in the uniform pair launch");
   constexpr bool F32 = TERMS == 0;
   static_assert(!F32 || (!FUSE && !SAVE), "the exact-fp32 form is the plain inference recurrence");
   static_assert(NW == 8, "waves 5..7 never own elements: they stage the input projection");
@@ -521,6 +534,16 @@ __global__ __launch_bounds__(64 * NW) void lstm_xcd_kernel(XcdArgs p) {
   __shared__ long long stamp_s[PROF ? STN * 24 : 1];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction: tell the compiler (scalar branches)
+  if constexpr (AUX) {
+    // not a member of any group: no barrier of theirs, no arrival, no word of p.sync or p.hx -- only the map, in the LDS of the
+    // partial sums (free here), and out
+    static_assert(sizeof(part_s) >= NTHR * 8 + 512, "the map's scratch fits the partial sums' LDS");
+    if ((int)blockIdx.x >= 8 * p.NU) {
+      kmeans2_map_workgroup<NTHR>(p.aux_feat, p.aux_per_utt, p.aux_db, p.aux_w, p.aux_stride, p.aux_iw, p.aux_dest, p.aux_D, p.B,
+                                  (int)blockIdx.x - 8 * p.NU, p.aux_n, part_s);
+      return;
+    }
+  }
   // group = workgroup id mod 8 (the XCD the dispatcher is observed to use); test bit 8 rotates the groups across
   // the XCDs instead, so that the placement-independent accesses run with real cross-XCD traffic
   const int ugi = blockIdx.x >> 3, g = (p.ablate & 8) ? ((blockIdx.x + ugi) & 7) : (blockIdx.x & 7);

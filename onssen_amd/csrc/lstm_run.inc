@@ -208,8 +208,12 @@ static int launch_xcd_pair(XcdArgs xa, hipStream_t st) {
   xa.row0 = 0;
   xa.nbg_a = ceil_div(xa.B, xa.RG);
   xa.nbg = 2 * xa.nbg_a;
-  const dim3 grid((unsigned)(8 * xa.NU));
+  // aux workgroups (uniform pairs only): at the END of the grid, so that the dispatcher hands them out after every member
+  if (xa.aux_n < 0 || (xa.aux_n > 0 && xa.frames)) return ONSSEN_E_ARG;
+  const dim3 grid((unsigned)(8 * xa.NU + xa.aux_n));
   if (xa.frames) hipLaunchKernelGGL((lstm_xcd_kernel<NT, 8, false, 3, true, false, true>), grid, dim3(512), 0, st, xa);
+  else if (xa.aux_n > 0 && xa.RG == 8) hipLaunchKernelGGL((lstm_xcd_kernel<NT, 8, false, 3, true, false, false, true>), grid, dim3(512), 0, st, xa);
+  else if (xa.aux_n > 0) hipLaunchKernelGGL((lstm_xcd_kernel<NT, 8, false, 3, false, false, false, true>), grid, dim3(512), 0, st, xa);
   else if (xa.RG == 8) hipLaunchKernelGGL((lstm_xcd_kernel<NT, 8, false, 3, true, false>), grid, dim3(512), 0, st, xa);
   else hipLaunchKernelGGL((lstm_xcd_kernel<NT, 8, false, 3, false, false>), grid, dim3(512), 0, st, xa);
   hipError_t e = hipGetLastError();
@@ -435,10 +439,12 @@ int onssen_lstm_train_forward_form_f32(const float* x, int64_t xs_b, int64_t xs_
 
 // ---- two-layer stack, software-pipelined over consecutive calls (round 6) -------------------------------------------
 // T_cap lays the workspace out (>= every T that passes through it); the uniform form has T_cap = T = T_prev and no frames
+// the target map of THIS batch, built by spare workgroups of the pair launch (uniform form): the clustering workspace, or all null / zero
+struct Pipe2Map { float db = 0.f; int D = 0; void* ws = nullptr; size_t ws_bytes = 0; };
 static int blstm_pipe2_impl(const float* x, int64_t xs_b, int64_t xs_t, int B, int T_cap, int T, const int32_t* frames, int T_prev,
                             const int32_t* frames_prev, int in_dim, int H, int ug, const float* const* wih_p_host,
                             const float* const* whh_p_host, const float* const* bias_p_host, void* ws, size_t ws_bytes, int flags,
-                            void* stream) {
+                            void* stream, const Pipe2Map& map = Pipe2Map()) {
   LstmGeo g;
   Pipe2Ws o;
   if (!lstm_geo(H, ug, &g)) return ONSSEN_E_ARG;
@@ -453,6 +459,13 @@ static int blstm_pipe2_impl(const float* x, int64_t xs_b, int64_t xs_t, int B, i
   if (ws_bytes < o.total) return ONSSEN_E_WORKSPACE;
   if (!aligned256(ws)) return ONSSEN_E_ALIGN;
   if (ug > 20 || g.NU > 32 || g.KQ2 > 24) return ONSSEN_E_ARG;
+  // the map's workspace: what onssen_dc_index_f32 asks of it; its features are x itself, so x is the dense [B][T][in_dim] array
+  const DcWs ml(B, T, in_dim, map.D);
+  if (map.ws) {
+    if (frames || map.D <= 0 || map.D > km::DMAX || xs_t != in_dim || xs_b != (int64_t)T * in_dim) return ONSSEN_E_ARG;
+    if (map.ws_bytes < ml.compact_bytes) return ONSSEN_E_WORKSPACE;
+    if (!aligned256(map.ws)) return ONSSEN_E_ALIGN;
+  }
   char* base = (char*)ws;
   float *G0 = (float*)(base + o.g0), *G1 = (float*)(base + o.g1);
   uint16_t *img_x = (uint16_t*)(base + o.img_x), *img0 = (uint16_t*)(base + o.img0), *img1 = (uint16_t*)(base + o.img1);
@@ -472,6 +485,11 @@ static int blstm_pipe2_impl(const float* x, int64_t xs_b, int64_t xs_t, int B, i
   xa.G_b = G0; xa.whh_b = (const unsigned short*)whh_p_host[0]; xa.yimg_b = img0; xa.T_b = T; xa.frames_b = frames;
   xa.ximg = img_x; xa.bias0 = bias_p_host[0]; xa.x0 = x; xa.xs_b = (long)xs_b; xa.xs_t = (long)xs_t;
   xa.terms = 3;
+  if (map.ws) {
+    xa.aux_n = B < 16 ? B : 16;      // two CUs per XCD are no member's
+    xa.aux_D = map.D; xa.aux_db = map.db; xa.aux_feat = x; xa.aux_per_utt = (long)T * in_dim; xa.aux_stride = ml.stride;
+    xa.aux_w = (float*)map.ws; xa.aux_iw = ml.at<int>(map.ws, ml.iw); xa.aux_dest = ml.at<int>(map.ws, ml.dest);
+  }
   ONSSEN_CLEAR_ERROR();
   rc = dispatch_ug<20>(ug, [&](auto ugc) { return launch_xcd_pair<decltype(ugc)::value / 4>(xa, (hipStream_t)stream); });
   if (rc != ONSSEN_OK || g_ready) return rc;
@@ -485,6 +503,17 @@ int onssen_blstm_pipe2_forward_f32(const float* x, int64_t xs_b, int64_t xs_t, i
                                    const float* const* bias_p_host, void* ws, size_t ws_bytes, int flags, void* stream) {
   return blstm_pipe2_impl(x, xs_b, xs_t, B, T, T, nullptr, T, nullptr, in_dim, H, ug, wih_p_host, whh_p_host, bias_p_host, ws, ws_bytes,
                           flags, stream);
+}
+
+int onssen_blstm_pipe2_map_forward_f32(const float* x, int64_t xs_b, int64_t xs_t, int B, int T, int in_dim, int H, int ug,
+                                       const float* const* wih_p_host, const float* const* whh_p_host,
+                                       const float* const* bias_p_host, void* ws, size_t ws_bytes, int flags, float db_threshold, int D,
+                                       void* map_ws, size_t map_ws_bytes, void* stream) {
+  if (!map_ws) return ONSSEN_E_ARG;
+  Pipe2Map map;
+  map.db = db_threshold; map.D = D; map.ws = map_ws; map.ws_bytes = map_ws_bytes;
+  return blstm_pipe2_impl(x, xs_b, xs_t, B, T, T, nullptr, T, nullptr, in_dim, H, ug, wih_p_host, whh_p_host, bias_p_host, ws, ws_bytes,
+                          flags, stream, map);
 }
 
 int onssen_blstm_pipe2_forward_ragged_f32(const float* x, int64_t xs_b, int64_t xs_t, int B, int T_cap, int T, const int32_t* frames,

@@ -574,8 +574,12 @@ class DCPipeline(_DCPipeCore):
     nearly what a 16-row group's does -- so ``push(batch n)`` runs, in ONE persistent launch, layer 1 of batch n-1 on half of the
     XCDs and layer 0 of batch n on the other half (``onssen_blstm_pipe2_forward_f32``), with the rest of both batches' work around it:
 
-        STFT, target map, input projection of batch n -> [ layer 1 (n-1) || layer 0 (n) ] -> layer 1's projection of batch n;
+        STFT, input projection of batch n -> [ layer 1 (n-1) || layer 0 (n) || target map (n) ] -> layer 1's projection of batch n;
         fc_dc (active bins only) + 2-means + masks + iSTFT of batch n-1
+
+    (the target map of batch n is first read by batch n's fc_dc, one step later: the persistent launch builds it in workgroups of
+    its own on the CUs its members leave free, ``onssen_blstm_pipe2_map_forward_f32``; ``aux_map=False`` builds it in front of the
+    launch with ``onssen_dc_index_f32`` instead -- the same bytes, three launches more on the critical path)
 
     and returns the separated batch n-1 -- (B, 2, n_samples), valid until the next-but-one ``push`` -- or None for the first
     batch; ``flush()`` drains the last one.  Every batch gets exactly the arithmetic ``separate_dc`` gives it on 16-row recurrence
@@ -588,7 +592,7 @@ class DCPipeline(_DCPipeCore):
     next ``push`` / ``flush`` (XcdAborted; ``separate_dc_stream`` re-runs the affected batches with ``separate_dc``).
     Two speakers only (the compacted clustering it ends in is the 2-means): ``separate_dc(num_speaker=)`` separates three or four."""
 
-    def __init__(self, model, B, n_samples, window_size=256, hop_size=64, db_threshold=40.0, iters=20, tol=1e-4, graph=True):
+    def __init__(self, model, B, n_samples, window_size=256, hop_size=64, db_threshold=40.0, iters=20, tol=1e-4, graph=True, aux_map=True):
         from .nn._core import _version_key
         why = _dc_pipe_why_not(model, B, window_size, 32)
         if why:
@@ -605,6 +609,7 @@ class DCPipeline(_DCPipeCore):
         self.masks = mk(B, T, F, 2)
         self.graphs = [None, None]
         self.use_graph = bool(graph)
+        self.aux_map = bool(aux_map)
         self._wkey = None
         self._version_key = _version_key
         self._prime()
@@ -616,10 +621,14 @@ class DCPipeline(_DCPipeCore):
         pk = self.model._packed.get(self.ug)
         lib.stft_logmag(self.wav[p].data_ptr(), B, self.n, self.n, self.nfft, self.hop, 1e-7, self.logmag[p].data_ptr(),
                         self.ri[p].data_ptr(), st)
-        lib.dc_index(self.logmag[p].data_ptr(), B, T, F, self.D, self.db, self.cws[p].data_ptr(), self.cnb, st)
-        lib.blstm_pipe2_forward(self.logmag[p].data_ptr(), T * F, F, B, T, F, self.H, self.ug,
-                                [t.data_ptr() for t in pk.wih_img], [t.data_ptr() for t in pk.whh_x3], [t.data_ptr() for t in pk.bias],
-                                self.ws.data_ptr(), self.wnb, self.flags, st)
+        weights = [t.data_ptr() for t in pk.wih_img], [t.data_ptr() for t in pk.whh_x3], [t.data_ptr() for t in pk.bias]
+        if self.aux_map:
+            lib.blstm_pipe2_map_forward(self.logmag[p].data_ptr(), T * F, F, B, T, F, self.H, self.ug, *weights, self.ws.data_ptr(), self.wnb,
+                                        self.flags, self.db, self.D, self.cws[p].data_ptr(), self.cnb, st)
+        else:
+            lib.dc_index(self.logmag[p].data_ptr(), B, T, F, self.D, self.db, self.cws[p].data_ptr(), self.cnb, st)
+            lib.blstm_pipe2_forward(self.logmag[p].data_ptr(), T * F, F, B, T, F, self.H, self.ug, *weights, self.ws.data_ptr(), self.wnb,
+                                    self.flags, st)
         if back_end:
             m = self.masks
             self._back_end(pk, 1 - p, T, self.comp_off, self.dest_off, self.ri[1 - p], (m.stride(0), m.stride(3), m.stride(1), m.stride(2)),
