@@ -745,6 +745,52 @@ int onssen_mag_istft_ragged_f32(const float* stft_ri, const float* mag, int64_t 
                                 float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Waveform-approximation training (Wang, Le Roux, Wang & Hershey 2018): the gradient through one inverse transform and the L1
+ * waveform loss under the best speaker permutation (csrc/istft_bwd.inc, csrc/loss_wa.inc).  No upstream counterpart.
+ *
+ * onssen_istft_backward_f32: the adjoint of onssen_mask_istft_f32 (mode 0), onssen_phase_istft_f32 (mode 1) and
+ * onssen_mag_istft_f32 (mode 2), uniform (frames = lengths = NULL) or ragged (both given), in one launch.  With g_out the
+ * gradient at the forward's `out` ((B, C, length) CONTIGUOUS float32; nothing of a row is read beyond lengths[b], so it counts
+ * as zero there), w the periodic Hann window, rw[n] the forward's reciprocal window sum of squares and a_f = 1 at DC / Nyquist, else 2:
+ *   G_c[t, f] = a_f * sum_i (w[i] / N) rw[n] g_out_c[n] e^{-2 pi i f i / N},   n = t hop + i - N/2
+ *   mode 0:  g_operand_c = Re X Re G + Im X Im G
+ *   mode 1:  g_operand_c = |X| (Re p_c Re G + Im p_c Im G),   g_phase_c = mask_c |X| (Re G, Im G)
+ *   mode 2:  g_operand_c = Re u Re G + Im u Im G,  u = X / |X| as the forward forms it ((1, 0) where X = 0)
+ * with the imaginary terms dropped at DC and Nyquist, as the forward ignores them; fp64 transform and products, one rounding.
+ *   g_operand (B, T, F, C) contiguous float32: the gradient at the masks (modes 0, 1) or magnitudes (mode 2)
+ *   g_phase   (C, B, T, F, 2) contiguous float32, 8-byte aligned, mode 1 only (NULL otherwise): the gradient at the phase maps
+ *   operand   the forward's masks with their strides: read in mode 1 only (for g_phase), may be NULL otherwise
+ *   phase, p_sc: as onssen_phase_istft_f32, mode 1 only
+ * Frames t >= frames[b] get zeros; nothing of X, the masks or the phases is read there.  Row b inside its own frames is bit for bit
+ * the uniform call on that utterance alone.  Deterministic, no atomics, no workspace.
+ * Refused before anything is launched: a NULL required pointer, B < 1, C < 1, T < 1, length < 1, hop < 1, hop > n_fft, n_fft not in
+ * {256, 512, 1024}, only one of frames / lengths, an unknown mode (ONSSEN_E_ARG); stft_ri, phase or g_phase off an 8-byte
+ * boundary, an odd p_sc (ONSSEN_E_ALIGN).
+ */
+int onssen_istft_backward_f32(const float* stft_ri, const float* operand, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf,
+                              const float* phase, int64_t p_sc, int mode, int B, int C, int T, const int32_t* frames, int n_fft, int hop,
+                              int length, const int32_t* lengths, const float* g_out, float* g_operand, float* g_phase, void* stream);
+/* The waveform L1 loss with the best permutation.  est (B, C, n) contiguous (the inverse transform's output); ref (b, j) at
+ * ref + b*r_sb + j*r_sc, unit sample stride, |stride| >= n; C <= 4.  Per row with n_b = lengths[b] valid samples (NULL: n; a device
+ * value is clamped to [1, n]):
+ *   D[i][j]  = sum_{t < n_b} |est_i[t] - ref_j[t]|   (fp64, fixed order)
+ *   value[b] = min over permutations p of sum_i D[i][p(i)] / (C n_b)   (lexicographic order, the first minimum wins)
+ *   perm[b]  = index of that permutation (nullable),   total[0] = sum_b value[b] / B (nullable)
+ *   d_est[b][i][t] = (g_value[b] + g_total[0] / B) * sign(est_i[t] - ref_p(i)[t]) / (C n_b),  0 at equality and at t >= n_b
+ * One pass over the signals forward (fp64 partial sums per chunk, merged in a fixed order: bit-repeatable, no atomics), one
+ * elementwise pass backward that reads the assignment the forward of the same batch left in ws.  d_est (B, C, n) contiguous.
+ * ws: caller-owned, 8-byte aligned, onssen_wa_pit_workspace_bytes(B, C) bytes (0 for a refused B or C), needs no zeroing.
+ * Refused before anything is launched or written: C < 1, C > 4, B < 1, B > 65535, n < 1, a NULL pointer (g_value and g_total both
+ * NULL), a row stride shorter than n (ONSSEN_E_ARG); a short ws (ONSSEN_E_WORKSPACE); a misaligned ws (ONSSEN_E_ALIGN).
+ */
+size_t onssen_wa_pit_workspace_bytes(int B, int C);
+int onssen_wa_pit_f32(const float* est, const float* ref, int64_t r_sb, int64_t r_sc, int B, int C, int n, const int32_t* lengths,
+                      float* value, int32_t* perm, float* total, void* ws, size_t ws_bytes, void* stream);
+int onssen_wa_pit_backward_f32(const float* est, const float* ref, int64_t r_sb, int64_t r_sc, int B, int C, int n,
+                               const int32_t* lengths, const float* g_value, const float* g_total, float* d_est, const void* ws,
+                               size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Ragged batches (round 4): the reference evaluates WHOLE utterances one at a time (onssen/utils/test.py:29-41 with the
  * batch-1 loader of onssen/data/wsj0_2mix.py:231-245), a shape that leaves most of the chip idle.  These entry points
  * run K utterances of different lengths in one launch sequence: every buffer keeps the padded batch shape (T = the longest

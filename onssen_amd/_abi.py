@@ -139,6 +139,11 @@ SIGNATURES = {
     "onssen_misi_phase_ragged_f32": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "onssen_mag_istft_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "onssen_mag_istft_ragged_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    # waveform-approximation training: the adjoint of the three inverse transforms, the L1 PIT waveform loss and its gradient
+    "onssen_istft_backward_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "onssen_wa_pit_workspace_bytes": (_sz, [_i, _i]),
+    "onssen_wa_pit_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "onssen_wa_pit_backward_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # deep-clustering separation without the embedding round trip (round 4)
     "onssen_dc_compact_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "onssen_dc_compact_layout": (_i, [_i, _i, _i, _i, _vp, _vp]),
@@ -664,6 +669,28 @@ class Lib:
             return
         self.check(self.dll.onssen_mag_istft_f32(stft_ri, mag, m_sb, m_sc, m_st, m_sf, B, Cn, T, n_fft, hop, length, out, stream),
                    "onssen_mag_istft_f32")
+
+    def istft_backward(self, stft_ri, operand, m_sb, m_sc, m_st, m_sf, phase, p_sc, mode, B, Cn, T, n_fft, hop, length, g_out,
+                       g_operand, g_phase, stream, frames=None, lengths=None):
+        """mode 0 / 1 / 2: the adjoint of mask_istft / phase_istft / mag_istft; g_out (B, C, length) contiguous."""
+        self.check(self.dll.onssen_istft_backward_f32(stft_ri, operand, m_sb, m_sc, m_st, m_sf, phase, p_sc, mode, B, Cn, T, frames,
+                                                      n_fft, hop, length, lengths, g_out, g_operand, g_phase, stream),
+                   "onssen_istft_backward_f32")
+
+    # ---- waveform-approximation loss: L1 distance with the best permutation ---
+    def wa_pit_workspace_bytes(self, B, Cn):
+        nb = int(self.dll.onssen_wa_pit_workspace_bytes(B, Cn))
+        if nb == 0:
+            self.check(-1, "onssen_wa_pit_workspace_bytes")
+        return nb
+
+    def wa_pit(self, est, ref, r_sb, r_sc, B, Cn, n, lengths, value, perm, total, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_wa_pit_f32(est, ref, r_sb, r_sc, B, Cn, n, lengths, value, perm, total, ws, ws_bytes, stream),
+                   "onssen_wa_pit_f32")
+
+    def wa_pit_backward(self, est, ref, r_sb, r_sc, B, Cn, n, lengths, g_value, g_total, d_est, ws, ws_bytes, stream):
+        self.check(self.dll.onssen_wa_pit_backward_f32(est, ref, r_sb, r_sc, B, Cn, n, lengths, g_value, g_total, d_est, ws, ws_bytes,
+                                                       stream), "onssen_wa_pit_backward_f32")
 
     def labels_enhance(self, noisy, clean, n_bins, mag_noisy, mag_clean, cos_diff, stream):
         self.check(self.dll.onssen_labels_enhance_f32(noisy, clean, n_bins, mag_noisy, mag_clean, cos_diff, stream),

@@ -7,6 +7,8 @@
 //                       with its phase flag the operand is mask * |X| * the network's phase estimate: onssen_phase_istft_f32)
 //   misi.inc            misi_phase_kernel (MISI phase reconstruction: mixture + C estimates -> residual spread over the speakers, fp64
 //                       STFT of two speakers per transform, Z / |Z|: the phase maps of the next onssen_phase_istft_f32)
+//   istft_bwd.inc       istft_bwd_kernel (waveform-approximation training: the adjoint of mask_istft_kernel in its three modes -- windowed
+//                       fp64 forward transform of the waveform gradient, two speakers per transform, gradients of masks / phases / magnitudes)
 //   gemm.inc            linear_x3q_kernel (K3/K7/K8/K9 on pre-split bf16 images: 256|128 x 320|256 tiles staged by LDS-DMA into a swizzled
 //                       layout, 8 waves, register epilogues), linear_x3p_kernel (round-1 form: 256x160 tiles; batched weight gradients;
 //                       bias | sigmoid | grouped L2-norm), linear_x3_kernel / linear_kernel (fp32-A forms, exact-fp32 MFMA),
@@ -28,6 +30,8 @@
 //   enhance.inc         labels_enhance_kernel (|X|, |S|, cos of the phase difference in one pass), loss_enhance_* (the MSA / PSA
 //                       enhancement losses: value and gradient); the reconstruction is mask_istft_kernel's magnitude mode (fft.inc)
 //   loss_upit.inc       loss_upit_* (the uPIT mask network's loss for 2 .. 4 speakers: pair sums in one pass, assignment scan, gradient)
+//   loss_wa.inc         wa_* (waveform-approximation training: L1 waveform distance under the best speaker permutation, fp64 sums in
+//                       one pass, assignment scan, sign gradient)
 //   resample.inc        resample_kernel (the loaders' sample-rate conversion: scipy's resample_poly as a polyphase filter over a ragged batch,
 //                       the tile's input span staged in the LDS as fp64, optional subtraction of a second signal on load)
 //   pack.inc            one-off weight re-layout (gate permutation, MFMA fragment order, BatchNorm fold); training glue: dropout,
@@ -132,6 +136,7 @@ static unsigned& xcd_spin_limit() {
 #include "lstm_run.inc"    // BLSTM host side: geometry, workspace layouts, launchers and the C ABI entries over lstm.inc / lstm_bwd.inc
 #include "fft.inc"
 #include "misi.inc"       // MISI phase reconstruction: the half-step between two inverse transforms (estimates -> phase maps)
+#include "istft_bwd.inc"  // waveform-approximation training: the adjoint of mask_istft_kernel, all three modes
 #include "loss_sdr.inc"
 #include "wav_io.inc"      // host code: the batch RIFF reader of the file loader
 #include "optim.inc"
@@ -145,6 +150,7 @@ static unsigned& xcd_spin_limit() {
 #include "enhance.inc"    // speech enhancement: training labels, the MSA / PSA losses and their gradient
 #include "loss_upit.inc"  // uPIT training: the utterance-level permutation-invariant mask loss for 2 .. 4 speakers and its gradient
 #include "resample.inc"   // file loaders: polyphase sample-rate conversion (scipy.signal.resample_poly) of a ragged batch
+#include "loss_wa.inc"    // waveform-approximation training: the L1 permutation-invariant waveform loss and its gradient
 
 // Co-tenant probe (tools/cotenant_probe.py): `workgroups` workgroups of `threads` threads that do nothing but hold their
 // CU for `ticks` ticks of the 100 MHz wall clock -- a stand-in for RCCL's channel kernels next to the persistent recurrences.
@@ -895,6 +901,13 @@ int onssen_misi_phase_ragged_f32(const float* mix, int64_t mix_stride, const flo
                                  int C, int n_max, const int32_t* n_per_utt, int n_fft, int hop, float* phase, void* stream) {
   if (!n_per_utt) return ONSSEN_E_ARG;
   return misi_phase_impl(mix, mix_stride, est, est_sb, est_sc, B, C, n_max, n_fft, hop, phase, stream, n_per_utt);
+}
+
+int onssen_istft_backward_f32(const float* stft_ri, const float* operand, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf,
+                              const float* phase, int64_t p_sc, int mode, int B, int C, int T, const int32_t* frames, int n_fft, int hop,
+                              int length, const int32_t* lengths, const float* g_out, float* g_operand, float* g_phase, void* stream) {
+  return istft_backward_impl(stft_ri, operand, m_sb, m_sc, m_st, m_sf, phase, p_sc, mode, B, C, T, frames, n_fft, hop, length, lengths,
+                             g_out, g_operand, g_phase, stream);
 }
 
 int onssen_mag_istft_f32(const float* stft_ri, const float* mag, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf, int B,

@@ -13,6 +13,10 @@ the host and yields ``(input_list, label_list)``.  There is no corpus here, so u
     "phase"     [feature_mix, phase_mix] , [one_hot, mag_mix, mag_s1, mag_s2, phase_s1, phase_s2]
     "upit"      [feature_mix] , [mag_mix, mag_s1 .. mag_sS]
     "upit-psa"  [feature_mix] , [mag_mix, mag_s1 .. mag_sS, cos_s1 .. cos_sS]      (S = feature_options' num_speaker, 2 .. 4; default 2)
+    "chimera-wa" [feature_mix] , [stft_ri_mix (B,L,F,2), sig_ref (B,2,n)]           waveform-approximation training (loss.loss_wa):
+    "upit-wa"    [feature_mix] , [stft_ri_mix (B,L,F,2), sig_ref (B,S,n)]           the mixture's cropped spectrum and the source
+                 waveforms under it, n = hop_size * (L - 1) samples from the centre of the crop's first frame -- the length
+                 ``mask_istft`` gives a crop of L frames by default, so estimate and reference line up sample for sample
     "conv-tasnet", "lstm-tasnet"   time-domain chunks (data/time_domain.py): [mix] , [s1, s2]
 
 ``one_hot`` is float64 like upstream's (np.zeros default, feature_utils.py:86; the losses cast).  Partition "tt" follows
@@ -27,7 +31,8 @@ from ..synthetic import synth_mixture, synth_mixture_k
 from . import time_domain
 
 
-UPIT_MODELS = ("upit", "upit-psa")
+UPIT_MODELS = ("upit", "upit-psa", "upit-wa")
+WA_MODELS = ("chimera-wa", "upit-wa")
 
 
 class SyntheticWsj02mix:
@@ -81,6 +86,20 @@ class SyntheticWsj02mix:
                     for k in range(self.num_speaker)]
             yield [feat], [labs[0][0]] + [l[1] for l in labs] + ([l[2] for l in labs] if self.model_name == "upit-psa" else [])
 
+    def _iter_wa(self):
+        rng = np.random.default_rng(self.seed)
+        B, L, S, hop = self.batch_size, self.frame_length, self.num_speaker, self.hop_size
+        for it in range(self.num_batches):
+            utts = [self._mixture(self.seed + it * B + b, self.n_samples) for b in range(B)]
+            wav = torch.from_numpy(np.stack([np.stack(u) for u in utts])).to(self.device)       # (B, 1 + S, n): on the device before the STFT
+            logmag, ri = stft_logmag(wav[:, 0].contiguous(), self.window_size, hop)
+            start = int(rng.integers(0, logmag.shape[1] - L))
+            feat = logmag[:, start:start + L].contiguous()
+            mix = ri[:, start:start + L].contiguous()
+            # frame t is centred on sample t * hop: the inverse transform of the crop returns the hop * (L - 1) samples from there
+            sig_ref = wav[:, 1:, start * hop:start * hop + hop * (L - 1)].contiguous()
+            yield [feat], [mix, sig_ref]
+
     def __len__(self):
         return self.num_batches
 
@@ -117,6 +136,9 @@ class SyntheticWsj02mix:
             return
         if self.partition == "tt":
             yield from self._iter_eval()
+            return
+        if self.model_name in WA_MODELS:
+            yield from self._iter_wa()
             return
         if self.model_name in UPIT_MODELS:
             yield from self._iter_upit()

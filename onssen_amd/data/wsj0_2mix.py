@@ -17,6 +17,11 @@ and ONE label-kernel launch (``onssen_labels_f32``).  Same
     "phase"     [feature_mix, phase_mix] , [one_hot, mag_mix, mag_s1, mag_s2, phase_s1, phase_s2]
     "upit"      [feature_mix] , [mag_mix, mag_s1, mag_s2]          "upit-psa": + [cos_s1, cos_s2]   (two speakers: the tree has s1 and s2)
 
+    "chimera-wa", "upit-wa"  [feature_mix] , [stft_ri_mix (B,L,F,2), sig_ref (B,2,n)]   waveform-approximation training
+                (loss.loss_wa): the mixture's cropped spectrum and the source waveforms under it, n = hop_size * (frame_length - 1)
+                samples from the centre of the crop's first frame (what ``mask_istft`` returns for the crop by default); a short
+                utterance is repeated like its frames, and the samples a frame would take beyond the file's end are 0
+
 Partitions "tr" / "cv": batches of ``batch_size`` in shuffled order (the reference's ``DataLoader(shuffle=True)``), an
 utterance of at most ``frame_length`` frames is repeated ``frame_length // T + 1`` times before the crop (``:118-123``).
 Partition "tt": whole utterances, batch 1, ``[feature_mix (1,T,F)] , [stft_r (1,T,F), stft_i (1,T,F), sig_ref (1,2,n)]`` with the
@@ -114,11 +119,11 @@ class Wsj02mixFiles:
     def __init__(self, model_name, feature_options, partition="tr", device="cuda:0", shuffle=None, seed=None):
         fo = feature_options
         g = (lambda k: fo[k]) if isinstance(fo, dict) else (lambda k: getattr(fo, k))
-        if model_name not in ("dc", "chimera", "chimera++", "phase", "upit", "upit-psa") + time_domain.MODELS:
+        if model_name not in ("dc", "chimera", "chimera++", "phase", "upit", "upit-psa", "chimera-wa", "upit-wa") + time_domain.MODELS:
             raise ValueError(f"unknown model_name {model_name!r}")
         self.model_name = model_name
         ns = fo.get("num_speaker", 2) if isinstance(fo, dict) else getattr(fo, "num_speaker", 2)
-        if model_name in ("upit", "upit-psa") and ns != 2:
+        if model_name in ("upit", "upit-psa", "upit-wa") and ns != 2:
             raise ValueError(f"feature_options num_speaker = {ns!r}: the mix/s1/s2 file tree holds two speakers")
         if model_name in time_domain.MODELS:     # time-domain chunks (data/time_domain.py): no STFT settings
             self.batch_size, self.sampling_rate, self.chunk_size = time_domain.options_of(model_name, fo)
@@ -217,8 +222,10 @@ class Wsj02mixFiles:
             starts[b] = int((rng or self.rng).integers(0, T * times - L))
         return slot, n_utt, starts
 
-    def _device_batch(self, item):
-        """Device side of one batch: (B, 3, L, F) log-magnitude and (B, 3, L, F, 2) spectrum of (mix, s1, s2), cropped."""
+    def _device_batch(self, item, with_sig_ref=False):
+        """Device side of one batch: (B, 3, L, F) log-magnitude and (B, 3, L, F, 2) spectrum of (mix, s1, s2), cropped.
+        ``with_sig_ref``: also the source waveforms under the crop, (B, 2, hop (L - 1)) -- sample n of the crop lies hop-offset
+        n % hop after the centre of its frame n // hop, which is frame (start + n // hop) % T of the (repeated) utterance."""
         slot, n_utt, starts = item
         B, L, hop = len(n_utt), self.frame_length, self.hop_size
         wav = slot.wav.to(self.device, non_blocking=True)               # ONE contiguous transfer from the pinned buffer
@@ -230,7 +237,16 @@ class Wsj02mixFiles:
         idx = torch.from_numpy((starts[:, None] + np.arange(L)[None, :]) % Tb[:, None]).to(self.device)   # wraps: the repeated utterance
         rows = torch.arange(B, device=self.device)[:, None, None]
         trip = torch.arange(3, device=self.device)[None, :, None]
-        return logmag.view(B, 3, T, F)[rows, trip, idx[:, None, :]], ri.view(B, 3, T, F, 2)[rows, trip, idx[:, None, :]]
+        crops = logmag.view(B, 3, T, F)[rows, trip, idx[:, None, :]], ri.view(B, 3, T, F, 2)[rows, trip, idx[:, None, :]]
+        if not with_sig_ref:
+            return crops
+        n = torch.arange(hop * (L - 1), device=self.device)
+        pos = idx[:, n // hop] * hop + (n % hop)[None, :]                                       # (B, hop (L - 1)) sample positions
+        inside = pos < torch.from_numpy(n_utt.astype(np.int64)).to(self.device)[:, None]
+        pos = torch.where(inside, pos, torch.zeros_like(pos))
+        src = wav.view(B, 3, -1)[:, 1:]                                                         # (B, 2, stride): s1, s2 on the device
+        sig_ref = torch.gather(src, 2, pos[:, None, :].expand(B, 2, -1)) * inside[:, None, :]
+        return crops + (sig_ref.contiguous(),)
 
     def host_batches(self, order=None, ring=None, rng=None):
         """Generator over the HOST side of the epoch's batches (``_read_batch`` items), synchronously on the calling thread.
@@ -309,6 +325,10 @@ class Wsj02mixFiles:
             return
         order = self.rng.permutation(len(self.file_list)) if self.shuffle else np.arange(len(self.file_list))
         for item in self._prefetched(order):
+            if self.model_name in ("chimera-wa", "upit-wa"):
+                logmag, ri, sig_ref = self._device_batch(item, with_sig_ref=True)
+                yield [logmag[:, 0].contiguous()], [ri[:, 0].contiguous(), sig_ref]
+                continue
             logmag, ri = self._device_batch(item)                   # (B, 3, L, F), (B, 3, L, F, 2)
             feat = logmag[:, 0].contiguous()
             mix, s1, s2 = (ri[:, i].contiguous() for i in range(3))

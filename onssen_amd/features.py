@@ -106,15 +106,105 @@ def resample(wav, rate_in, rate_out, lengths=None, sub=None):
     return y, lengths_out
 
 
+# ---- training through the inverse transforms (waveform approximation: csrc/istft_bwd.inc) ----------------------------------------
+ISTFT_MASK, ISTFT_PHASE, ISTFT_MAG = 0, 1, 2
+
+
+def _wants_grad(*ts):
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in ts)
+
+
+def _refuse_spectrum_grad(name, stft_ri):
+    if torch.is_grad_enabled() and stft_ri.requires_grad:
+        raise RuntimeError(f"{name}: stft_ri requires a gradient; the mixture's spectrum is data -- the backward gives the gradient "
+                           f"of the masks / magnitudes (and phases) only")
+
+
+def _phase_maps(phases, C, shape):
+    """C phase maps (a list, or one (C,B,T,F,2) tensor) -> (tensors kept alive until the launch is queued, pointer, distance in
+    floats): read where they are when they lie at one common 8-byte-aligned distance, otherwise stacked first."""
+    phases = [p.float().contiguous() for p in (phases.unbind(0) if torch.is_tensor(phases) else phases)]
+    if len(phases) != C or any(tuple(p.shape) != shape for p in phases):
+        raise ValueError(f"phase_istft: expected {C} phase maps of shape {shape}, got {[tuple(p.shape) for p in phases]}")
+    step = {phases[c + 1].data_ptr() - phases[c].data_ptr() for c in range(C - 1)}
+    if len(step) > 1 or any(d % 8 for d in step) or phases[0].data_ptr() % 8:
+        stacked = torch.stack(phases)                    # kept alive until the launch is queued
+        phases = list(stacked.unbind(0))
+        step = {phases[1].data_ptr() - phases[0].data_ptr()}
+    return phases, phases[0].data_ptr(), (step.pop() // 4 if step else 0)
+
+
+class _IstftGrad(torch.autograd.Function):
+    """mask_istft / phase_istft / mag_istft with their backward on the device.  The forward is the plain call on the detached
+    inputs (the same launch, the same bits); the backward is ``onssen_istft_backward_f32``: one launch from the gradient at the
+    (B, C, length) waveforms to the gradient at the masks / magnitudes (B,T,F,C) and, in the phase mode, at the C phase maps.
+    ``operand`` is (B,T,F,C) with any strides; the phase maps follow one by one, or as one (C,B,T,F,2) tensor (``stacked``)."""
+
+    @staticmethod
+    def forward(ctx, mode, hop, length, frames, lengths, stacked, stft_ri, operand, *phases):
+        stft_ri, operand = stft_ri.detach(), operand.detach()
+        ph = None
+        if mode == ISTFT_PHASE:
+            ph = phases[0].detach() if stacked else [p.detach() for p in phases]
+            out = phase_istft(stft_ri, operand, ph, hop, length, frames, lengths)
+        elif mode == ISTFT_MAG:
+            out = mag_istft(stft_ri, operand, hop, length, frames, lengths)
+        else:
+            out = mask_istft(stft_ri, operand, hop, length, frames, lengths)
+        ctx.saved = (stft_ri, operand, ph, frames, lengths)
+        ctx.geom = (mode, hop, out.shape[2], stacked, len(phases))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        mode, hop, length, stacked, n_ph = ctx.geom
+        stft_ri, operand, ph, frames, lengths = ctx.saved
+        stft_ri, operand = stft_ri.float().contiguous(), operand.float()
+        B, T, F, C = operand.shape
+        g = g.float().contiguous()
+        g_op = torch.empty(B, T, F, C, device=g.device, dtype=torch.float32)
+        g_ph, keep, p_ptr, p_sc = None, None, None, 0
+        if mode == ISTFT_PHASE:
+            keep, p_ptr, p_sc = _phase_maps(ph, C, (B, T, F, 2))
+            g_ph = torch.empty(C, B, T, F, 2, device=g.device, dtype=torch.float32)
+        rag = {}
+        if frames is not None:
+            rag = dict(frames=frames.data_ptr(), lengths=lengths.data_ptr())      # (int32 device tensors, kept by the node)
+        get_lib().istft_backward(stft_ri.data_ptr(), operand.data_ptr(), operand.stride(0), operand.stride(3), operand.stride(1),
+                                 operand.stride(2), p_ptr, p_sc, mode, B, C, T, 2 * (F - 1), hop, length, g.data_ptr(), g_op.data_ptr(),
+                                 g_ph.data_ptr() if g_ph is not None else None, _stream(), **rag)
+        d_ph = () if mode != ISTFT_PHASE else ((g_ph,) if stacked else tuple(g_ph.unbind(0)))
+        return (None, None, None, None, None, None, None, g_op, *d_ph, *([None] * (n_ph - len(d_ph))))
+
+
+def _ragged_for_grad(name, frames, lengths, B, T, length, device):
+    """The ragged extents as the int32 device tensors both passes of the node read (validated once)."""
+    if (frames is None) != (lengths is None):
+        raise ValueError(f"{name}: a ragged batch needs both frames= and lengths=")
+    if frames is None:
+        return None, None
+    return _lengths_i32(frames, B, T, device, "frames"), _lengths_i32(lengths, B, length, device, "lengths")
+
+
 def mask_istft(stft_ri, masks, hop_size=64, length=None, frames=None, lengths=None):
     """stft_ri (B,T,F,2); masks (B,T,F,C) (any strides) or None ->
     (B, C, length) float32: istft(stft * mask_c) per speaker, librosa
     semantics (hop, length=nsample).
 
     ``frames`` / ``lengths`` (B,): a RAGGED batch -- row b has frames[b] <= T frames and lengths[b] <= length output
-    samples (zeros after them); inside them the result is bit for bit that of a batch-1 call on that utterance."""
+    samples (zeros after them); inside them the result is bit for bit that of a batch-1 call on that utterance.
+
+    Differentiable with respect to ``masks``: when autograd is on and they require a gradient, the same launch runs inside an
+    autograd node whose backward is ``onssen_istft_backward_f32`` (csrc/istft_bwd.inc); a ``stft_ri`` that requires one raises."""
     if not stft_ri.is_cuda:
         raise RuntimeError("mask_istft: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
+    _refuse_spectrum_grad("mask_istft", stft_ri)
+    if _wants_grad(masks):
+        B, T = stft_ri.shape[:2]
+        n = hop_size * (T - 1) if length is None else length
+        frames, lengths = _ragged_for_grad("mask_istft", frames, lengths, B, T, n, stft_ri.device)
+        return _IstftGrad.apply(ISTFT_MASK, hop_size, n, frames, lengths, False, stft_ri, masks.float())
     stft_ri = stft_ri.float().contiguous()
     B, T, F, _ = stft_ri.shape
     n_fft = 2 * (F - 1)
@@ -150,11 +240,24 @@ def phase_istft(stft_ri, masks, phases, hop_size=64, length=None, frames=None, l
     as phase_net's forward returns them; any two fp32 tensors); otherwise they are stacked first.
 
     ``frames`` / ``lengths`` (B,): a RAGGED batch exactly as in ``mask_istft`` (both or neither).  ``out``: a (B, C, length)
-    float32 contiguous tensor to write into instead of a new one (``separation.misi`` re-uses one across its iterations)."""
+    float32 contiguous tensor to write into instead of a new one (``separation.misi`` re-uses one across its iterations).
+
+    Differentiable with respect to ``masks`` and ``phases`` as ``mask_istft`` is with respect to its masks (``out=`` together
+    with an input that requires a gradient raises)."""
     if (frames is None) != (lengths is None):
         raise ValueError("phase_istft: a ragged batch needs both frames= and lengths=")
     if not stft_ri.is_cuda:
         raise RuntimeError("phase_istft: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
+    _refuse_spectrum_grad("phase_istft", stft_ri)
+    if _wants_grad(masks, *([phases] if torch.is_tensor(phases) else phases)):
+        if out is not None:
+            raise ValueError("phase_istft: out= cannot be combined with inputs that require a gradient")
+        B, T = stft_ri.shape[:2]
+        n = hop_size * (T - 1) if length is None else length
+        frames, lengths = _ragged_for_grad("phase_istft", frames, lengths, B, T, n, stft_ri.device)
+        stacked = torch.is_tensor(phases)
+        return _IstftGrad.apply(ISTFT_PHASE, hop_size, n, frames, lengths, stacked, stft_ri, masks.float(),
+                                *([phases.float()] if stacked else [p.float() for p in phases]))
     stft_ri = stft_ri.float().contiguous()
     B, T, F, _ = stft_ri.shape
     n_fft = 2 * (F - 1)
@@ -167,20 +270,13 @@ def phase_istft(stft_ri, masks, phases, hop_size=64, length=None, frames=None, l
         rag = dict(frames=frames.data_ptr(), lengths=lengths.data_ptr())
     masks = masks.float()
     C = masks.shape[3]
-    phases = [p.float().contiguous() for p in (phases.unbind(0) if torch.is_tensor(phases) else phases)]
-    if len(phases) != C or any(tuple(p.shape) != (B, T, F, 2) for p in phases):
-        raise ValueError(f"phase_istft: expected {C} phase maps of shape {(B, T, F, 2)}, got {[tuple(p.shape) for p in phases]}")
-    step = {phases[c + 1].data_ptr() - phases[c].data_ptr() for c in range(C - 1)}
-    if len(step) > 1 or any(d % 8 for d in step) or phases[0].data_ptr() % 8:
-        stacked = torch.stack(phases)                    # kept alive until the launch below is queued
-        phases = list(stacked.unbind(0))
-        step = {phases[1].data_ptr() - phases[0].data_ptr()}
+    phases, p_ptr, p_sc = _phase_maps(phases, C, (B, T, F, 2))
     if out is None:
         out = torch.empty(B, C, length, device=stft_ri.device, dtype=torch.float32)
     elif tuple(out.shape) != (B, C, length) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != stft_ri.device:
         raise ValueError(f"phase_istft: out must be a contiguous float32 tensor of shape {(B, C, length)} on {stft_ri.device}")
     get_lib().phase_istft(stft_ri.data_ptr(), masks.data_ptr(), masks.stride(0), masks.stride(3), masks.stride(1), masks.stride(2),
-                          phases[0].data_ptr(), step.pop() // 4 if step else 0, B, C, T, n_fft, hop_size, length, out.data_ptr(),
+                          p_ptr, p_sc, B, C, T, n_fft, hop_size, length, out.data_ptr(),
                           _stream(), **rag)
     return out
 
@@ -245,9 +341,20 @@ def mag_istft(stft_ri, mags, hop_size=64, length=None, frames=None, lengths=None
     reconstruction of the enhancement recipe (the ``enhance`` network returns a clean magnitude, not a mask).  A bin whose
     spectrum is exactly 0 has phase 0, as np.angle gives it.
 
-    ``frames`` / ``lengths`` (B,): a RAGGED batch exactly as in ``mask_istft``."""
+    ``frames`` / ``lengths`` (B,): a RAGGED batch exactly as in ``mask_istft``.  Differentiable with respect to ``mags`` as
+    ``mask_istft`` is with respect to its masks."""
     if not stft_ri.is_cuda:
         raise RuntimeError("mag_istft: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
+    _refuse_spectrum_grad("mag_istft", stft_ri)
+    if _wants_grad(mags):
+        B, T, F = stft_ri.shape[:3]
+        if mags.dim() == 3:
+            mags = mags.unsqueeze(-1)
+        if tuple(mags.shape[:3]) != (B, T, F):
+            raise ValueError(f"mag_istft: expected magnitudes of shape {(B, T, F)} (+ channels), got {tuple(mags.shape)}")
+        n = hop_size * (T - 1) if length is None else length
+        frames, lengths = _ragged_for_grad("mag_istft", frames, lengths, B, T, n, stft_ri.device)
+        return _IstftGrad.apply(ISTFT_MAG, hop_size, n, frames, lengths, False, stft_ri, mags.float())
     stft_ri = stft_ri.float().contiguous()
     B, T, F, _ = stft_ri.shape
     n_fft = 2 * (F - 1)

@@ -12,6 +12,9 @@ The enhancement losses (``loss_mask_msa`` / ``loss_mask_psa``, onssen/loss/loss_
 ``onssen_loss_enhance_f32`` and gradient from ``onssen_loss_enhance_grad_f32`` (csrc/enhance.inc), routed like the chimera losses.
 The uPIT losses (``loss_upit_msa`` / ``loss_upit_psa``; upstream has none): the permutation-invariant mask loss for 2 .. 4 speakers on
 ``onssen_loss_upit_f32`` / ``onssen_loss_upit_grad_f32`` (csrc/loss_upit.inc), routed the same way.
+The waveform-approximation loss (``wa_pit`` / ``loss_wa``; upstream has none): the network's masks go through one differentiable
+inverse transform (features.mask_istft / phase_istft / mag_istft, backward csrc/istft_bwd.inc) and the waveforms are compared in L1
+under the best speaker permutation on ``onssen_wa_pit_f32`` / ``onssen_wa_pit_backward_f32`` (csrc/loss_wa.inc).
 Semantics follow onssen/loss/loss_dc.py:6-44 and loss_util.py:4-11 exactly,
 including their quirks: the affinity terms are Frobenius *norms* (not squared
 norms) and the final product ``(B,) * (B,1)`` broadcasts to a (B, B) tensor
@@ -861,3 +864,145 @@ def sisnr_pit(ests, refs, lengths=None, return_perm=False):
     cannot take (``sisnr_pit_limits``); shapes that differ raise ``sisnr``'s RuntimeError."""
     value, _, perm = _sisnr_pit_apply(list(ests), list(refs), lengths)
     return (value, perm.long()) if return_perm else value
+
+
+# ----------------------------------------------------------------------------- waveform approximation
+WA_PIT_MAX_SPEAKERS = 4
+WA_KINDS = ("chimera", "upit", "phase", "enhance")
+
+
+def _wa_ref_rows(ref, n):
+    """The references as the kernels read them: fp32, unit sample stride, rows (batch and speaker) at least n samples apart."""
+    ref = ref.detach().float()
+    B, C, _ = ref.shape
+    if ref.stride(2) != 1 or (C > 1 and abs(ref.stride(1)) < n) or (B > 1 and abs(ref.stride(0)) < n):
+        ref = ref.contiguous()
+    return ref
+
+
+def _wa_pit_launch(est, ref, lengths):
+    from .hip import get_lib
+    lib = get_lib()
+    B, C, n = est.shape
+    dev = est.device
+    nbytes = lib.wa_pit_workspace_bytes(B, C)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    value = torch.empty(B, device=dev, dtype=torch.float32)
+    perm = torch.empty(B, device=dev, dtype=torch.int32)
+    lib.wa_pit(est.data_ptr(), ref.data_ptr(), ref.stride(0) if B > 1 else C * n, ref.stride(1) if C > 1 else n, B, C, n,
+               None if lengths is None else lengths.data_ptr(), value.data_ptr(), perm.data_ptr(), None, ws.data_ptr(), nbytes,
+               torch.cuda.current_stream().cuda_stream)
+    return value, perm, ws
+
+
+class _WaPitHip(torch.autograd.Function):
+    """(V (B,), perm (B,) int32) of the waveform L1 loss with the best permutation on ``onssen_wa_pit_f32``; the estimates'
+    gradient comes from ``onssen_wa_pit_backward_f32``, which reads the assignment the forward left in its workspace
+    (csrc/loss_wa.inc).  ``est`` (B, C, n) contiguous fp32; the references get no gradient."""
+
+    @staticmethod
+    def forward(ctx, est, ref, lengths):
+        est = est.detach()
+        value, perm, ws = _wa_pit_launch(est, ref, lengths)
+        ctx.mark_non_differentiable(perm)
+        ctx.sig = (est, ref, lengths, ws)            # the workspace is owned by the graph: the backward reads the assignment in it
+        return value, perm
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_value, _g_perm):
+        from .hip import get_lib
+        est, ref, lengths, ws = ctx.sig
+        B, C, n = est.shape
+        g_value = g_value.float().contiguous()
+        d = torch.empty_like(est)
+        get_lib().wa_pit_backward(est.data_ptr(), ref.data_ptr(), ref.stride(0) if B > 1 else C * n, ref.stride(1) if C > 1 else n,
+                                  B, C, n, None if lengths is None else lengths.data_ptr(), g_value.data_ptr(), None, d.data_ptr(),
+                                  ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+        return d, None, None
+
+
+def wa_pit(est, ref, lengths=None, return_perm=False):
+    """The waveform-approximation objective of Wang, Le Roux, Wang & Hershey 2018 per row: est, ref (B, C, n) fp32 on a ROCm device,
+    C <= 4 ->  V (B,) = min over the C! assignments p of sum_i sum_t |est_i[t] - ref_p(i)[t]| / (C n_b), differentiable with
+    respect to ``est`` (d est = sign(est - ref_p) / (C n_b), 0 at equality).  ``return_perm``: also the index (B,) int64 of each
+    row's assignment in the order of ``itertools.permutations(range(C))`` (the first minimum wins).  ``lengths`` (B,), host
+    integers or an int32 device tensor: row b is its first n_b = lengths[b] samples; the gradient beyond them is zero.
+    ``ref`` is read where it is with any batch and speaker strides (unit sample stride); it gets no gradient.
+    Runs on the kernels of csrc/loss_wa.inc: one pass over the signals forward (fp64 sums, fixed order), one elementwise pass
+    backward, nothing read back by the host, bit-repeatable, capturable in a graph.  There is no PyTorch-op route."""
+    if est.dim() != 3 or ref.dim() != 3 or est.shape != ref.shape:
+        raise ValueError(f"wa_pit: expected est and ref of one shape (B, C, n), got {tuple(est.shape)} and {tuple(ref.shape)}")
+    B, C, n = est.shape
+    if not 1 <= C <= WA_PIT_MAX_SPEAKERS:
+        raise ValueError(f"wa_pit: {C} speakers; the kernels take 1 .. {WA_PIT_MAX_SPEAKERS}")
+    if B < 1 or n < 1:
+        raise ValueError(f"wa_pit: empty signals, {tuple(est.shape)}")
+    if torch.is_grad_enabled() and ref.requires_grad:
+        raise RuntimeError("wa_pit: a reference requires a gradient; the backward gives the estimates' gradient only")
+    if not est.is_cuda or not ref.is_cuda:
+        raise RuntimeError("wa_pit: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
+    lengths = _pit_lengths(lengths, B, n, est.device)
+    ref = _wa_ref_rows(ref, n)
+    est = est.float().contiguous()
+    if torch.is_grad_enabled() and est.requires_grad:
+        value, perm = _WaPitHip.apply(est, ref, lengths)
+    else:
+        value, perm, _ = _wa_pit_launch(est.detach(), ref, lengths)
+    return (value, perm.long()) if return_perm else value
+
+
+def loss_wa(output, label, hop_size=64, frames=None, lengths=None, kind="chimera", misi_iters=0):
+    """Waveform-approximation training loss (Wang, Le Roux, Wang & Hershey 2018; upstream has none): the network's output goes
+    through ONE inverse transform and is compared with the source waveforms, ``wa_pit(...).mean()``.
+
+    ``label`` = [stft_ri_mix (B,T,F,2), sig_ref (B,C,n)] (the "chimera-wa" / "upit-wa" loaders); n is the length of the
+    reconstruction (``hop_size * (T - 1)`` from those loaders).  ``kind`` says what ``output`` is -- the arity alone cannot (a
+    chimera output and three uPIT masks are both three tensors):
+      "chimera"  [embedding, mask_A, mask_B] of chimera / chimera++: the two masks through ``mask_istft``, the embedding ignored
+      "upit"     the S masks of the uPIT network, through ``mask_istft``
+      "phase"    [embedding, mask_A, mask_B, phase_A, phase_B] of the phase network, through ``phase_istft``
+      "enhance"  [magnitude] of the enhancement network, through ``mag_istft``: one channel, the identity assignment
+    ``frames`` / ``lengths`` (B,): a ragged batch as in ``mask_istft`` (both or neither); ``lengths`` also bounds the loss's sums.
+    ``misi_iters``: unfolded MISI iterations as training layers need the adjoint of ``misi_phase``; anything but 0 raises
+    NotImplementedError.  The mixture's spectrum is data: a ``stft_ri`` that requires a gradient raises."""
+    from . import features
+    if misi_iters != 0:
+        raise NotImplementedError(f"loss_wa: misi_iters = {misi_iters!r}; training through unfolded MISI iterations needs the adjoint of "
+                                  f"misi_phase (its reflect padding and the Z / |Z| Jacobian), which is not built -- only misi_iters = 0 is")
+    if kind not in WA_KINDS:
+        raise ValueError(f"loss_wa: unknown kind {kind!r}; one of {WA_KINDS}")
+    output = list(output)
+    want = {"chimera": (3,), "phase": (5,), "enhance": (1,), "upit": (2, 3, 4)}[kind]
+    if len(output) not in want:
+        raise ValueError(f"loss_wa: {len(output)} output tensors for kind {kind!r}, which has {' or '.join(map(str, want))}")
+    if len(label) != 2:
+        raise ValueError(f"loss_wa: {len(label)} label tensors; the label is [stft_ri_mix (B,T,F,2), sig_ref (B,C,n)]")
+    stft_ri, sig_ref = label
+    if stft_ri.dim() != 4 or stft_ri.shape[-1] != 2 or sig_ref.dim() != 3:
+        raise ValueError(f"loss_wa: expected stft_ri_mix (B,T,F,2) and sig_ref (B,C,n), got {tuple(stft_ri.shape)} and {tuple(sig_ref.shape)}")
+    if stft_ri.requires_grad:
+        raise RuntimeError("loss_wa: stft_ri_mix requires a gradient; the mixture's spectrum is data")
+    masks = output[1:3] if kind in ("chimera", "phase") else output
+    B, T, F = stft_ri.shape[:3]
+    for m in masks:
+        if tuple(m.shape) != (B, T, F):
+            raise ValueError(f"loss_wa: an output of shape {tuple(m.shape)} for a spectrum of {(B, T, F)} bins")
+    if tuple(sig_ref.shape[:2]) != (B, len(masks)):
+        raise ValueError(f"loss_wa: sig_ref {tuple(sig_ref.shape)} for a batch of {B} with {len(masks)} estimates")
+    if (frames is None) != (lengths is None):
+        raise ValueError("loss_wa: a ragged batch needs both frames= and lengths=")
+    n = sig_ref.shape[2]
+    rag = dict(frames=frames, lengths=lengths)
+    if kind == "enhance":
+        est = features.mag_istft(stft_ri, masks[0], hop_size, n, **rag)
+    else:
+        base = _upit_masks_base(masks)               # the network's own interleaved buffer when the masks are its planes
+        if kind == "phase":
+            for p in output[3:]:
+                if tuple(p.shape) != (B, T, F, 2):
+                    raise ValueError(f"loss_wa: a phase map of shape {tuple(p.shape)}, expected {(B, T, F, 2)}")
+            est = features.phase_istft(stft_ri, base, output[3:], hop_size, n, **rag)
+        else:
+            est = features.mask_istft(stft_ri, base, hop_size, n, **rag)
+    return wa_pit(est, sig_ref, lengths).mean()
