@@ -23,8 +23,8 @@
 //                       Lloyd iterations in one persistent launch with register-resident rows; launch-per-iteration fallback)
 //   kmeans_k.inc        kmeansk_* (the same back end for 2 .. 4 speakers: farthest-point initialisation, launch-per-iteration Lloyd,
 //                       K-channel masks)
-//   loss_sdr.inc        loss_dc_* (value and gradient) / loss_mask_* (chimera mask term: value, winning assignment, gradient),
-//                       sdr_* (batch SI-SDR with best permutation, fp64 sums)
+//   loss_sdr.inc        loss_dc_* (value and gradient), sdr_* (batch SI-SDR with best permutation, fp64 sums)
+//   loss_mask.inc       loss_mask_* (chimera mask term: value, winning assignment, gradient)
 //   loss_sisnr.inc      sisnr_* (Conv-TasNet's SI-SNR permutation-invariant training loss: value, assignment, gradient; fp64 moments)
 //   loss_phase.inc      loss_phase_* (phase_net's training loss: mask term and cosine phase term in one pass, assignment, gradient)
 //   enhance.inc         labels_enhance_kernel (|X|, |S|, cos of the phase difference in one pass), loss_enhance_* (the MSA / PSA
@@ -138,6 +138,7 @@ static unsigned& xcd_spin_limit() {
 #include "misi.inc"       // MISI phase reconstruction: the half-step between two inverse transforms (estimates -> phase maps)
 #include "istft_bwd.inc"  // waveform-approximation training: the adjoint of mask_istft_kernel, all three modes
 #include "loss_sdr.inc"
+#include "loss_mask.inc"  // chimera training: the mask-inference term (better of the two speaker assignments) and its gradient
 #include "wav_io.inc"      // host code: the batch RIFF reader of the file loader
 #include "optim.inc"
 #include "tasnet.inc"     // Conv-TasNet forward: its kernels and its C ABI entries
@@ -441,40 +442,6 @@ int onssen_batch_sdr_ragged_f32(const float* est, const float* org, const float*
                                 void* stream) {
   if (!lengths) return ONSSEN_E_ARG;
   return batch_sdr_impl(est, org, mask, B, C, n, sdr_out, perm_out, ws, ws_bytes, stream, lengths);
-}
-
-size_t onssen_loss_mask_workspace_bytes(int B) { return B > 0 ? (size_t)B * 32 * 4 * sizeof(float) : 0; }
-
-int onssen_loss_mask_f32(const float* mask_a, const float* mask_b, int64_t m_sb, int64_t m_se, const float* mag_mix,
-                         const float* mag_s1, const float* mag_s2, const float* cos_s1, const float* cos_s2, int B, int TF,
-                         float* out, int32_t* perm_out, void* ws, size_t ws_bytes, void* stream) {
-  if (!mask_a || !mask_b || !mag_mix || !mag_s1 || !mag_s2 || !out || !ws || B <= 0 || TF <= 0 ||
-      ((cos_s1 == nullptr) != (cos_s2 == nullptr)))
-    return ONSSEN_E_ARG;
-  if (ws_bytes < onssen_loss_mask_workspace_bytes(B)) return ONSSEN_E_WORKSPACE;
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(loss_mask_kernel, dim3(32, (unsigned)B), dim3(256), 0, st, mask_a, mask_b, (long)m_sb, (long)m_se, mag_mix,
-                     mag_s1, mag_s2, cos_s1, cos_s2, TF, (float*)ws);
-  hipLaunchKernelGGL(loss_mask_final_kernel, dim3((unsigned)B), dim3(64), 0, st, (const float*)ws, 32, out, (int*)perm_out);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-int onssen_loss_mask_grad_f32(const float* mask_a, const float* mask_b, int64_t m_sb, int64_t m_se, const float* mag_mix,
-                              const float* mag_s1, const float* mag_s2, const float* cos_s1, const float* cos_s2, int B, int TF,
-                              const float* g, const int32_t* perm, float* d_mask_a, float* d_mask_b, int64_t d_sb, int64_t d_se,
-                              void* stream) {
-  if (!mask_a || !mask_b || !mag_mix || !mag_s1 || !mag_s2 || !g || !perm || !d_mask_a || !d_mask_b || B <= 0 || TF <= 0 ||
-      ((cos_s1 == nullptr) != (cos_s2 == nullptr)))
-    return ONSSEN_E_ARG;
-  ONSSEN_CLEAR_ERROR();
-  const int nblk = ceil_div(TF, 256) < 64 ? ceil_div(TF, 256) : 64;
-  hipLaunchKernelGGL(loss_mask_grad_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(256), 0, (hipStream_t)stream, mask_a, mask_b,
-                     (long)m_sb, (long)m_se, mag_mix, mag_s1, mag_s2, cos_s1, cos_s2, TF, g, (const int*)perm, d_mask_a, d_mask_b,
-                     (long)d_sb, (long)d_se);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
 }
 
 // ---- training: weight images for the backward recurrence (the training forward and the backward itself: lstm_run.inc) ----

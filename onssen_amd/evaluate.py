@@ -321,9 +321,9 @@ class tester_upit(tester):
         self.hop_size, self.misi_iters = hop_size, _misi_iters(misi_iters, "tester_upit")
 
     def get_est_sig(self, input, label, output, frames=None, lengths=None):
-        from .loss import _upit_masks_base
+        from .loss import _planes_base
         ri, sig_ref = _mix_ri(label)
-        masks = _upit_masks_base(list(output))            # the network's (B,T,F,S) buffer when the masks are its planes
+        masks = _planes_base(list(output))            # the network's (B,T,F,S) buffer when the masks are its planes
         return _misi_est(ri, masks, self.hop_size, sig_ref.shape[-1], self.misi_iters, frames, lengths), sig_ref.float()
 
 

@@ -1,7 +1,8 @@
 """Training losses needed by the data-parallel step.
 
 Chimera losses (onssen/loss/loss_chimera.py): the deep-clustering term as below, the mask-inference term on
-``onssen_loss_mask_f32`` (value; the winning speaker assignment) and ``onssen_loss_mask_grad_f32`` (gradient, one pass).
+``onssen_loss_mask_f32`` (value; the winning speaker assignment) and ``onssen_loss_mask_grad_f32`` (gradient, one pass;
+csrc/loss_mask.inc).
 On a GPU the loss_dc value comes from ``onssen_loss_dc_f32`` (one pass over the embedding builds the Gram of ``[V | Y]``) and, when
 autograd needs it, the gradient from ``onssen_loss_dc_grad_f32`` (``dV = Z M`` from the same Gram: one more pass); on the CPU
 (tests, the gloo path) PyTorch ops with the same single-Gram forward and analytic backward.  ``ONSSEN_LOSS_HIP=0`` keeps the
@@ -9,9 +10,22 @@ PyTorch form on the GPU.
 The phase network's loss (``loss_phase``): the same deep-clustering term, and the mask term and cosine phase term from
 ``onssen_loss_phase_f32`` / ``onssen_loss_phase_grad_f32`` (one pass over the eleven maps forward, one elementwise pass backward).
 The enhancement losses (``loss_mask_msa`` / ``loss_mask_psa``, onssen/loss/loss_mask.py): one estimate against one target, value from
-``onssen_loss_enhance_f32`` and gradient from ``onssen_loss_enhance_grad_f32`` (csrc/enhance.inc), routed like the chimera losses.
+``onssen_loss_enhance_f32`` and gradient from ``onssen_loss_enhance_grad_f32`` (csrc/enhance.inc).
 The uPIT losses (``loss_upit_msa`` / ``loss_upit_psa``; upstream has none): the permutation-invariant mask loss for 2 .. 4 speakers on
-``onssen_loss_upit_f32`` / ``onssen_loss_upit_grad_f32`` (csrc/loss_upit.inc), routed the same way.
+``onssen_loss_upit_f32`` / ``onssen_loss_upit_grad_f32`` (csrc/loss_upit.inc).
+
+Routing.  The chimera mask term, the enhancement losses and the uPIT losses choose their form in ``_route``: "value" (ROCm tensors
+and no gradient wanted: the value kernel alone), "grad" (a gradient wanted and option ``loss`` = "1": an autograd node over the value
+and the gradient kernel), else "aten" (PyTorch ops; always on the CPU, and for what the kernels do not take).  Two losses route by
+rules of their own: ``loss_dc`` (its kernels bound D + C and, for the gradient, C) and ``loss_phase`` (HIP whenever
+option ``loss`` = "1", with or without a gradient: "hip" | "aten").  ``last_enhance_path`` / ``last_upit_path`` /
+``last_phase_path`` / ``last_si_snr_path`` say which route the last call of a family took.
+
+Plane buffers.  The mask networks write their S masks as the planes ``buf[..., k]`` of one contiguous fp32 (..., S) buffer.
+``_planes_base`` hands that buffer itself to the kernels and to autograd when the masks are exactly its planes (the graph then runs
+through the root tensor, not through S select views whose gradients would be scattered into zeros and added); anything else is
+interleaved by ``torch.stack`` first.  Every mask-family node takes the (..., S) buffer; labels are detached fp32 contiguous maps,
+workspaces are allocated per call (nothing cached: every route can be captured in a graph).
 The waveform-approximation loss (``wa_pit`` / ``loss_wa``; upstream has none): the network's masks go through one differentiable
 inverse transform (features.mask_istft / phase_istft / mag_istft, backward csrc/istft_bwd.inc) and the waveforms are compared in L1
 under the best speaker permutation on ``onssen_wa_pit_f32`` / ``onssen_wa_pit_backward_f32`` (csrc/loss_wa.inc).
@@ -25,6 +39,83 @@ import os
 import torch
 
 from . import options
+
+
+# ----------------------------------------------------------------------------- shared host path of the HIP routes
+def _lib():
+    from .hip import get_lib
+    return get_lib()
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _lab(t):
+    """A label map as the kernels read it: detached (labels carry no gradient), fp32, contiguous.  None passes through."""
+    return None if t is None else t.detach().float().contiguous()
+
+
+def _grad_in(g):
+    """An incoming gradient as the gradient kernels read it (None: that output was not used)."""
+    return None if g is None else g.float().contiguous()
+
+
+def _ws(nbytes, device):
+    """A workspace of this call alone."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _no_grad_needed(*ts):
+    return not (torch.is_grad_enabled() and any(t.requires_grad for t in ts))
+
+
+def _route(is_cuda, needs_grad, eligible=True):
+    """Which form a mask-family loss takes: "value" (a ROCm tensor and no gradient wanted: the value kernel), "grad" (a gradient
+    wanted and option ``loss`` = "1": the autograd node over the two kernels), else "aten" (PyTorch ops; always on the CPU, and
+    when the kernels cannot take the call: ``eligible`` false)."""
+    if not (is_cuda and eligible):
+        return "aten"
+    if not needs_grad:
+        return "value"
+    return "grad" if options.get("loss") == "1" else "aten"
+
+
+_enhance_route = _route                 # (is_cuda, needs_grad): the name the enhancement losses introduced it under
+
+
+def _planes_base(masks):
+    """The contiguous fp32 (*mask.shape, S) buffer whose S planes the masks are: the network's own when every mask is plane k of
+    one contiguous fp32 buffer of exactly S * numel elements (offset ``base.storage_offset() + k``, strides S times the dense
+    ones, equal shapes; the root may be the head's flat (B, T, F S) output: the same memory), else ``torch.stack`` of them."""
+    S, m0 = len(masks), masks[0]
+    base = getattr(m0, "_base", None)
+    dense, acc = [], S
+    for n_i in reversed(m0.shape):
+        dense.insert(0, acc)
+        acc *= n_i
+    dense = tuple(dense)
+    if (base is not None and base.dtype == torch.float32 and base.is_contiguous() and base.numel() == S * m0.numel()
+            and all(getattr(m, "_base", None) is base and m.stride() == dense and m.shape == m0.shape
+                    and m.storage_offset() == base.storage_offset() + k for k, m in enumerate(masks))):
+        return base if base.shape == (*m0.shape, S) else base.view(*m0.shape, S)
+    return torch.stack([m.float() for m in masks], -1)
+
+
+def _rows(t):
+    """(B, elements per batch row) of a map (B, ...), without the view ``t[0]`` would make."""
+    return t.shape[0], t.numel() // t.shape[0]
+
+
+def _two_planes(t):
+    """(plane 0, plane 1, batch stride, element stride in floats) of an interleaved fp32 (B, ..., 2) buffer, as the chimera and
+    phase entries take their two mask maps."""
+    p = t.data_ptr()
+    return p, p + 4, _rows(t)[1], 2
 
 
 def _fro(x):
@@ -146,31 +237,17 @@ def _mask_term(mask_A, mask_B, mag_mix, t1, t2):
     return torch.min(l_ab, l_ba)
 
 
-def _mask_term_hip(mask_A, mask_B, mag_mix, s1, s2, c1=None, c2=None):
-    """The mask-inference term on the device (no autograd): one pass over the maps, onssen_loss_mask_f32."""
-    from .hip import get_lib
-    B = mag_mix.shape[0]
-    TF = mag_mix[0].numel()
-    base = getattr(mask_A, "_base", None)
-    if (base is None or getattr(mask_B, "_base", None) is not base or mask_A.stride() != mask_B.stride()
-            or mask_A.stride(2) * mask_A.shape[2] != mask_A.stride(1)):
-        mask_A, mask_B = mask_A.contiguous(), mask_B.contiguous()   # not the strided views of one (B,T,F,2) buffer
-    if mask_A.dtype != torch.float32 or mask_B.dtype != torch.float32:   # autocast / a user-supplied half estimate: the kernel reads fp32
-        mask_A, mask_B = mask_A.float().contiguous(), mask_B.float().contiguous()
-    f32 = lambda t: None if t is None else t.float().contiguous()
-    mag, s1, s2, c1, c2 = f32(mag_mix), f32(s1), f32(s2), f32(c1), f32(c2)
-    out = torch.empty(B, device=mag.device, dtype=torch.float32)
-    lib = get_lib()
-    ws = torch.empty(lib.loss_mask_workspace_bytes(B), dtype=torch.uint8, device=mag.device)
-    # element (b, e = t*F + f) of a mask view sits at b*stride(0) + e*stride(2) when stride(1) = F*stride(2)
-    lib.loss_mask(mask_A.data_ptr(), mask_B.data_ptr(), mask_A.stride(0), mask_A.stride(2), mag.data_ptr(), s1.data_ptr(),
-                  s2.data_ptr(), c1.data_ptr() if c1 is not None else None, c2.data_ptr() if c2 is not None else None,
-                  B, TF, out.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
-    return out
-
-
-def _no_grad_needed(*ts):
-    return not (torch.is_grad_enabled() and any(t.requires_grad for t in ts))
+def _mask_term_launch(mask_a, mask_b, m_sb, m_se, mag, s1, s2, c1, c2, want_perm):
+    """onssen_loss_mask_f32 over two mask maps given as pointers, element (b, e) of each at b * m_sb + e * m_se floats ->
+    (out (B,), the winning assignment (B,) int32 or None)."""
+    lib = _lib()
+    (B, TF), dev = _rows(mag), mag.device
+    out = torch.empty(B, device=dev, dtype=torch.float32)
+    perm = torch.empty(B, device=dev, dtype=torch.int32) if want_perm else None
+    ws = _ws(lib.loss_mask_workspace_bytes(B), dev)
+    lib.loss_mask(mask_a, mask_b, m_sb, m_se, mag.data_ptr(), s1.data_ptr(), s2.data_ptr(), _ptr(c1), _ptr(c2), B, TF,
+                  out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), perm=_ptr(perm))
+    return out, perm
 
 
 class _MaskTermHip(torch.autograd.Function):
@@ -181,118 +258,80 @@ class _MaskTermHip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, masks, mag, s1, s2, c1, c2):
-        from .hip import get_lib
-        lib = get_lib()
-        B = mag.shape[0]
-        TF = mag[0].numel()
-        out = torch.empty(B, device=mag.device, dtype=torch.float32)
-        perm = torch.empty(B, device=mag.device, dtype=torch.int32)
-        ws = torch.empty(lib.loss_mask_workspace_bytes(B), dtype=torch.uint8, device=mag.device)
-        p = masks.data_ptr()
-        lib.loss_mask(p, p + 4, 2 * TF, 2, mag.data_ptr(), s1.data_ptr(), s2.data_ptr(),
-                      c1.data_ptr() if c1 is not None else None, c2.data_ptr() if c2 is not None else None, B, TF,
-                      out.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream, perm=perm.data_ptr())
+        out, perm = _mask_term_launch(*_two_planes(masks), mag, s1, s2, c1, c2, True)
         ctx.save_for_backward(masks, mag, s1, s2, perm, *([c1, c2] if c1 is not None else []))
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        from .hip import get_lib
         masks, mag, s1, s2, perm, *cs = ctx.saved_tensors
         c1, c2 = cs if cs else (None, None)
-        B = mag.shape[0]
-        TF = mag[0].numel()
         d = torch.empty_like(masks)
-        g = g.float().contiguous()
-        p, q = masks.data_ptr(), d.data_ptr()
-        get_lib().loss_mask_grad(p, p + 4, 2 * TF, 2, mag.data_ptr(), s1.data_ptr(), s2.data_ptr(),
-                                 c1.data_ptr() if c1 is not None else None, c2.data_ptr() if c2 is not None else None, B, TF,
-                                 g.data_ptr(), perm.data_ptr(), q, q + 4, 2 * TF, 2, torch.cuda.current_stream().cuda_stream)
+        g = _grad_in(g)
+        _lib().loss_mask_grad(*_two_planes(masks), mag.data_ptr(), s1.data_ptr(), s2.data_ptr(), _ptr(c1), _ptr(c2), *_rows(mag),
+                              g.data_ptr(), perm.data_ptr(), *_two_planes(d), _stream())
         return d, None, None, None, None, None
 
 
-def _mask_term_hip_autograd(mask_A, mask_B, mag_mix, s1, s2, c1=None, c2=None):
-    """Mask term WITH a gradient on the HIP kernels.  The network's two masks are strided views of one (B,T,F,2) buffer
-    (onssen/nn/chimera.py:42-45): the Function is applied to that buffer itself (the autograd graph runs through the root
-    tensor, not through two select views whose gradients would be scattered into zeros and added); anything else is
-    interleaved by torch.stack first."""
+def _mask_term_hip(route, mask_A, mask_B, mag_mix, s1, s2, c1=None, c2=None):
+    """The mask-inference term on the device.  "grad": the node over the plane buffer.  "value" is the one place that does not
+    go through ``_planes_base``: the kernel reads any two maps of one batch and one element stride, so two views of one base
+    with common strides (the planes of a buffer of any width, say) and two separate contiguous tensors are read where they lie,
+    without the copy an interleaved buffer would cost an evaluation."""
+    mag, s1, s2, c1, c2 = _lab(mag_mix), _lab(s1), _lab(s2), _lab(c1), _lab(c2)
+    if route == "grad":
+        return _MaskTermHip.apply(_planes_base((mask_A, mask_B)), mag, s1, s2, c1, c2)
     base = getattr(mask_A, "_base", None)
-    dense, acc = [], 2                              # strides of a map whose elements are 2 apart in a contiguous buffer
-    for n_i in reversed(mask_A.shape):
-        dense.insert(0, acc)
-        acc *= n_i
-    if not (base is not None and getattr(mask_B, "_base", None) is base and base.dtype == torch.float32 and base.is_contiguous()
-            and base.numel() == 2 * mask_A.numel() and mask_A.stride() == mask_B.stride() == tuple(dense)
-            and mask_A.storage_offset() == base.storage_offset() and mask_B.storage_offset() == base.storage_offset() + 1):
-        base = torch.stack([mask_A.float(), mask_B.float()], -1)
-    f32 = lambda t: None if t is None else t.detach().float().contiguous()
-    return _MaskTermHip.apply(base, f32(mag_mix), f32(s1), f32(s2), f32(c1), f32(c2))
+    if (base is None or getattr(mask_B, "_base", None) is not base or mask_A.stride() != mask_B.stride()
+            or mask_A.stride(2) * mask_A.shape[2] != mask_A.stride(1)):
+        mask_A, mask_B = mask_A.contiguous(), mask_B.contiguous()
+    if mask_A.dtype != torch.float32 or mask_B.dtype != torch.float32:   # autocast / a user-supplied half estimate: the kernel reads fp32
+        mask_A, mask_B = mask_A.float().contiguous(), mask_B.float().contiguous()
+    # element (b, e = t*F + f) of a mask view sits at b*stride(0) + e*stride(2) when stride(1) = F*stride(2)
+    return _mask_term_launch(mask_A.data_ptr(), mask_B.data_ptr(), mask_A.stride(0), mask_A.stride(2), mag, s1, s2, c1, c2, False)[0]
 
 
-def _use_hip_mask_grad(mask_A):
-    return mask_A.is_cuda and options.get("loss") == "1"
+def _loss_chimera(embedding, mask_A, mask_B, one_hot, mag_mix, mag_s1, mag_s2, cos_s1=None, cos_s2=None):
+    le = loss_dc([embedding], [one_hot, mag_mix])
+    route = _route(mask_A.is_cuda, not _no_grad_needed(mask_A, mask_B))
+    if route != "aten":
+        lm = _mask_term_hip(route, mask_A, mask_B, mag_mix, mag_s1, mag_s2, cos_s1, cos_s2)
+    elif cos_s1 is None:
+        lm = _mask_term(mask_A, mask_B, mag_mix, mag_s1, mag_s2)
+    else:
+        lm = _mask_term(mask_A, mask_B, mag_mix, torch.min(mag_mix, torch.relu(mag_s1 * cos_s1)),
+                        torch.min(mag_mix, torch.relu(mag_s2 * cos_s2)))
+    return le * 0.975 + lm * 0.025
 
 
 def loss_chimera_msa(output, label):
     """onssen/loss/loss_chimera.py:6-31: 0.975 * loss_dc + 0.025 * magnitude-spectrum-approximation mask loss with the
     better of the two speaker assignments ((B,B) like loss_dc, as upstream)."""
-    embedding, mask_A, mask_B = output
-    one_hot, mag_mix, mag_s1, mag_s2 = label
-    le = loss_dc([embedding], [one_hot, mag_mix])
-    if mask_A.is_cuda and _no_grad_needed(mask_A, mask_B):
-        lm = _mask_term_hip(mask_A, mask_B, mag_mix, mag_s1, mag_s2)
-    elif _use_hip_mask_grad(mask_A):
-        lm = _mask_term_hip_autograd(mask_A, mask_B, mag_mix, mag_s1, mag_s2)
-    else:
-        lm = _mask_term(mask_A, mask_B, mag_mix, mag_s1, mag_s2)
-    return le * 0.975 + lm * 0.025
+    (embedding, mask_A, mask_B), (one_hot, mag_mix, mag_s1, mag_s2) = output, label
+    return _loss_chimera(embedding, mask_A, mask_B, one_hot, mag_mix, mag_s1, mag_s2)
 
 
 def loss_chimera_psa(output, label):
     """onssen/loss/loss_chimera.py:33-59: as MSA with the phase-sensitive targets min(|x|, relu(|s| cos(theta)))."""
-    embedding, mask_A, mask_B = output
-    one_hot, mag_mix, mag_s1, mag_s2, cos_s1, cos_s2 = label
-    le = loss_dc([embedding], [one_hot, mag_mix])
-    if mask_A.is_cuda and _no_grad_needed(mask_A, mask_B):
-        lm = _mask_term_hip(mask_A, mask_B, mag_mix, mag_s1, mag_s2, cos_s1, cos_s2)
-    elif _use_hip_mask_grad(mask_A):
-        lm = _mask_term_hip_autograd(mask_A, mask_B, mag_mix, mag_s1, mag_s2, cos_s1, cos_s2)
-    else:
-        t1 = torch.min(mag_mix, torch.relu(mag_s1 * cos_s1))
-        t2 = torch.min(mag_mix, torch.relu(mag_s2 * cos_s2))
-        lm = _mask_term(mask_A, mask_B, mag_mix, t1, t2)
-    return le * 0.975 + lm * 0.025
+    (embedding, mask_A, mask_B), (one_hot, mag_mix, mag_s1, mag_s2, cos_s1, cos_s2) = output, label
+    return _loss_chimera(embedding, mask_A, mask_B, one_hot, mag_mix, mag_s1, mag_s2, cos_s1, cos_s2)
 
 
 # ----------------------------------------------------------------------------- enhancement losses
 last_enhance_path = None
 
 
-def _enhance_route(is_cuda, needs_grad):
-    """Which form an enhancement loss takes, as the chimera losses choose: "value" (a ROCm tensor and no gradient wanted: the
-    value kernel), "grad" (a gradient wanted and option ``loss`` = "1": the autograd node over the two kernels), else "aten"
-    (PyTorch ops; always on the CPU)."""
-    if not is_cuda:
-        return "aten"
-    if not needs_grad:
-        return "value"
-    return "grad" if options.get("loss") == "1" else "aten"
-
-
-def _enhance_launch(mode, est, mag_noisy, mag_clean, cos_diff, scale, want_total):
-    from .hip import get_lib
-    lib = get_lib()
-    B = est.shape[0]
-    TF = est[0].numel()
-    dev = est.device
+def _enhance_launch(mode, est, mag_noisy, mag_clean, cos_diff, scale):
+    """onssen_loss_enhance_f32 -> MSA: the scalar ``scale * sum (est - clean)^2``; PSA (mag_noisy given): the sums (B,)."""
+    lib = _lib()
+    (B, TF), dev = _rows(est), est.device
     per_utt = torch.empty(B, device=dev, dtype=torch.float32)
-    total = torch.empty((), device=dev, dtype=torch.float32) if want_total else None
-    ws = torch.empty(lib.loss_enhance_workspace_bytes(B), dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    lib.loss_enhance(mode, est.data_ptr(), ptr(mag_noisy), mag_clean.data_ptr(), ptr(cos_diff), B, TF, scale, per_utt.data_ptr(),
-                     ptr(total), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
-    return per_utt, total
+    total = torch.empty((), device=dev, dtype=torch.float32) if mag_noisy is None else None
+    ws = _ws(lib.loss_enhance_workspace_bytes(B), dev)
+    lib.loss_enhance(mode, est.data_ptr(), _ptr(mag_noisy), mag_clean.data_ptr(), _ptr(cos_diff), B, TF, scale, per_utt.data_ptr(),
+                     _ptr(total), ws.data_ptr(), ws.numel(), _stream())
+    return per_utt if total is None else total
 
 
 class _EnhanceLossHip(torch.autograd.Function):
@@ -302,39 +341,37 @@ class _EnhanceLossHip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mode, scale, est, mag_noisy, mag_clean, cos_diff):
-        from . import _abi
-        msa = mode == _abi.ENHANCE_MSA
-        per_utt, total = _enhance_launch(mode, est, mag_noisy, mag_clean, cos_diff, scale, msa)
         ctx.geom = (mode, scale)
-        ctx.save_for_backward(est, mag_clean, *([] if msa else [mag_noisy, cos_diff]))
-        return total if msa else per_utt
+        ctx.save_for_backward(est, mag_clean, *([] if mag_noisy is None else [mag_noisy, cos_diff]))
+        return _enhance_launch(mode, est, mag_noisy, mag_clean, cos_diff, scale)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        from .hip import get_lib
         mode, scale = ctx.geom
         est, mag_clean, *rest = ctx.saved_tensors
         mag_noisy, cos_diff = rest if rest else (None, None)
         d = torch.empty_like(est)
-        g = g.float().contiguous()
-        ptr = lambda t: None if t is None else t.data_ptr()
-        get_lib().loss_enhance_grad(mode, est.data_ptr(), ptr(mag_noisy), mag_clean.data_ptr(), ptr(cos_diff), est.shape[0],
-                                    est[0].numel(), scale, g.data_ptr(), d.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        g = _grad_in(g)
+        _lib().loss_enhance_grad(mode, est.data_ptr(), _ptr(mag_noisy), mag_clean.data_ptr(), _ptr(cos_diff), *_rows(est), scale,
+                                 g.data_ptr(), d.data_ptr(), _stream())
         return None, None, d, None, None, None
 
 
-def _enhance_hip(mode, route, est, mag_noisy, mag_clean, cos_diff, scale):
+def _loss_enhance(est, mag_noisy, mag_clean, cos_diff, aten):
+    """One estimate against one target: MSA (mag_noisy and cos_diff None) or PSA; ``aten()`` is the form on PyTorch ops."""
+    global last_enhance_path
     from . import _abi
-    lab = lambda t: None if t is None else t.detach().float().contiguous()
-    mag_noisy, mag_clean, cos_diff = lab(mag_noisy), lab(mag_clean), lab(cos_diff)
-    shape = est.shape
+    same = all(t is None or t.shape == est.shape for t in (mag_noisy, mag_clean, cos_diff))
+    route = last_enhance_path = _route(est.is_cuda, not _no_grad_needed(est), same and est.dim() >= 2)
+    if route == "aten":
+        return aten()
+    mode, scale = (_abi.ENHANCE_MSA, 1.0 / est.numel()) if mag_noisy is None else (_abi.ENHANCE_PSA, 1.0)
+    mag_noisy, mag_clean, cos_diff = _lab(mag_noisy), _lab(mag_clean), _lab(cos_diff)
     x = est.float().contiguous()
     if route == "grad":
         return _EnhanceLossHip.apply(mode, scale, x, mag_noisy, mag_clean, cos_diff)
-    msa = mode == _abi.ENHANCE_MSA
-    per_utt, total = _enhance_launch(mode, x.detach(), mag_noisy, mag_clean, cos_diff, scale, msa)
-    return total if msa else per_utt
+    return _enhance_launch(mode, x.detach(), mag_noisy, mag_clean, cos_diff, scale)
 
 
 def loss_mask_msa(output, label):
@@ -346,17 +383,11 @@ def loss_mask_msa(output, label):
     On ROCm tensors the value comes from ``onssen_loss_enhance_f32`` when no gradient is wanted, value and gradient from the
     autograd node over the enhancement loss kernels with option ``loss`` = "1"; otherwise, and always on the CPU, PyTorch ops.
     ``last_enhance_path`` ("value" | "grad" | "aten") says which route the last call took."""
-    global last_enhance_path
-    from . import _abi
     assert len(output) == 1, "There must be 1 tensor in the output"
     assert len(label) == 2, "There must be 2 tensors in the label"
     clean_est, = output
     mag_clean, _cos_diff = label
-    route = last_enhance_path = _enhance_route(clean_est.is_cuda, not _no_grad_needed(clean_est))
-    if route == "aten" or clean_est.shape != mag_clean.shape or clean_est.dim() < 2:
-        last_enhance_path = "aten"
-        return torch.nn.functional.mse_loss(clean_est, mag_clean)
-    return _enhance_hip(_abi.ENHANCE_MSA, route, clean_est, None, mag_clean, None, 1.0 / clean_est.numel())
+    return _loss_enhance(clean_est, None, mag_clean, None, lambda: torch.nn.functional.mse_loss(clean_est, mag_clean))
 
 
 def loss_mask_psa(output, label):
@@ -366,18 +397,12 @@ def loss_mask_psa(output, label):
     [mag_clean, cos_diff], mag_noisy travels with the input) nor what ``enhance`` returns (a magnitude, not a mask): upstream's
     recipe trains with ``loss_mask_msa``, and so does this one; a caller with a mask-valued model builds the label list itself.
     Routes as ``loss_mask_msa``."""
-    global last_enhance_path
-    from . import _abi
     assert len(output) == 1, "There must be 1 tensor in the output"
     assert len(label) == 3, "There must be 3 tensors in the label"
     mask, = output
     mag_noisy, mag_clean, cos_diff = label
-    route = last_enhance_path = _enhance_route(mask.is_cuda, not _no_grad_needed(mask))
-    same = mask.shape == mag_noisy.shape == mag_clean.shape == cos_diff.shape
-    if route == "aten" or not same or mask.dim() < 2:
-        last_enhance_path = "aten"
-        return _l1(mask * mag_noisy - torch.min(mag_noisy, torch.relu(mag_clean * cos_diff)))
-    return _enhance_hip(_abi.ENHANCE_PSA, route, mask, mag_noisy, mag_clean, cos_diff, 1.0)
+    return _loss_enhance(mask, mag_noisy, mag_clean, cos_diff,
+                         lambda: _l1(mask * mag_noisy - torch.min(mag_noisy, torch.relu(mag_clean * cos_diff))))
 
 
 # ----------------------------------------------------------------------------- uPIT losses (2 .. 4 speakers)
@@ -400,26 +425,10 @@ def _upit_aten(masks, mag_mix, targets):
     return out, perm
 
 
-def _upit_masks_base(masks):
-    """The contiguous (..., S) fp32 buffer whose S planes the masks are (the network's own when all are views of one, as
-    _mask_term_hip_autograd checks for two; anything else is interleaved by torch.stack)."""
-    S, m0 = len(masks), masks[0]
-    base = getattr(m0, "_base", None)
-    dense, acc = [], S
-    for n_i in reversed(m0.shape):
-        dense.insert(0, acc)
-        acc *= n_i
-    if (base is not None and base.dtype == torch.float32 and base.is_contiguous() and base.numel() == S * m0.numel()
-            and all(getattr(m, "_base", None) is base and m.stride() == tuple(dense) and m.shape == m0.shape
-                    and m.storage_offset() == base.storage_offset() + k for k, m in enumerate(masks))):
-        return base.view(*m0.shape, S)          # (the root may be the head's (B, T, F S) output: the same memory)
-    return torch.stack([m.float() for m in masks], -1)
-
-
 def _upit_maps(maps):
     """S label maps of one shape -> (first pointer's tensor list kept alive, pointer, distance in floats): the maps as they lie
     when they sit at one common distance (slices of one tensor, say), else stacked first."""
-    maps = [t.detach().float().contiguous() for t in maps]
+    maps = [_lab(t) for t in maps]
     ptrs = [t.data_ptr() for t in maps]
     d = ptrs[1] - ptrs[0]
     if d % 4 == 0 and all(ptrs[j] - ptrs[0] == j * d for j in range(len(maps))):
@@ -435,16 +444,14 @@ def _upit_frames(frames, B, T, device):
     return as_frames(frames, B, T, device)
 
 
-def _upit_launch(base, S, mag, src, cs, frames, F, want_perm=True):
-    from .hip import get_lib
-    lib = get_lib()
-    B, TF, dev = mag.shape[0], mag[0].numel(), mag.device
+def _upit_launch(base, S, mag, src, cs, frames, F):
+    lib = _lib()
+    (B, TF), dev = _rows(mag), mag.device
     out = torch.empty(B, device=dev, dtype=torch.float32)
     perm = torch.empty(B, device=dev, dtype=torch.int32)
-    ws = torch.empty(lib.loss_upit_workspace_bytes(B, S), dtype=torch.uint8, device=dev)
+    ws = _ws(lib.loss_upit_workspace_bytes(B, S), dev)
     lib.loss_upit(base.data_ptr(), TF * S, S, 1, mag.data_ptr(), src[1], src[2], cs[1] if cs else None, cs[2] if cs else 0,
-                  frames.data_ptr() if frames is not None else None, F, B, TF, S, out.data_ptr(), perm.data_ptr(), None,
-                  ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+                  _ptr(frames), F, B, TF, S, out.data_ptr(), perm.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream())
     return out, perm
 
 
@@ -464,16 +471,15 @@ class _UpitLossHip(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g, _g_perm):
-        from .hip import get_lib
         S, src, cs, ragged, F = ctx.geom
         base, mag, perm, *rest = ctx.saved_tensors
         frames = rest[-1] if ragged else None
-        B, TF = mag.shape[0], mag[0].numel()
+        B, TF = _rows(mag)
         d = torch.empty_like(base)
-        g = g.float().contiguous()
-        get_lib().loss_upit_grad(base.data_ptr(), TF * S, S, 1, mag.data_ptr(), src[0], src[1], cs[0] if cs else None,
-                                 cs[1] if cs else 0, frames.data_ptr() if ragged else None, F, B, TF, S, g.data_ptr(),
-                                 perm.data_ptr(), d.data_ptr(), TF * S, S, 1, torch.cuda.current_stream().cuda_stream)
+        g = _grad_in(g)
+        _lib().loss_upit_grad(base.data_ptr(), TF * S, S, 1, mag.data_ptr(), src[0], src[1], cs[0] if cs else None,
+                              cs[1] if cs else 0, _ptr(frames), F, B, TF, S, g.data_ptr(), perm.data_ptr(), d.data_ptr(),
+                              TF * S, S, 1, _stream())
         return d, None, None, None, None, None, None
 
 
@@ -487,15 +493,8 @@ def _loss_upit(name, output, label, psa, frames, return_perm):
                          f"([mag_mix, mag_s1 .. mag_s{S}" + (f", cos_s1 .. cos_s{S}])" if psa else "])"))
     mag_mix, mags, coss = label[0], list(label[1:1 + S]), (list(label[1 + S:]) if psa else None)
     m0 = masks[0]
-    needs_grad = not _no_grad_needed(*masks)
     same = all(t.shape == m0.shape for t in masks + [mag_mix] + mags + (coss or []))
-    if not m0.is_cuda or S > UPIT_MAX_SPEAKERS or not same or m0.dim() < 2:
-        route = "aten"
-    elif not needs_grad:
-        route = "value"
-    else:
-        route = "grad" if options.get("loss") == "1" else "aten"
-    last_upit_path = route
+    route = last_upit_path = _route(m0.is_cuda, not _no_grad_needed(*masks), S <= UPIT_MAX_SPEAKERS and same and m0.dim() >= 2)
     if route == "aten":
         if frames is not None:
             raise RuntimeError(f"{name}: frames=... (ragged batch) needs the HIP kernels (ROCm tensors, at most "
@@ -507,10 +506,10 @@ def _loss_upit(name, output, label, psa, frames, return_perm):
         return (out, perm) if return_perm else out
     B = m0.shape[0]
     F = m0.shape[-1]
-    frames = _upit_frames(frames, B, m0[0].numel() // F, m0.device)
-    mag = mag_mix.detach().float().contiguous()
+    frames = _upit_frames(frames, B, _rows(m0)[1] // F, m0.device)
+    mag = _lab(mag_mix)
     src, cs = _upit_maps(mags), (_upit_maps(coss) if psa else None)
-    base = _upit_masks_base(masks)
+    base = _planes_base(masks)
     if route == "grad":
         out, perm = _UpitLossHip.apply(base, S, mag, src, cs, frames, F)
     else:
@@ -554,35 +553,16 @@ def _phase_terms(mask_A, mask_B, phase_A, phase_B, mag_mix, mag_s1, mag_s2, phas
     return torch.where(straight, l1, l2), torch.where(straight, p1, p2)
 
 
-def _phase_interleaved_masks(mask_A, mask_B):
-    """The contiguous (..., 2) fp32 buffer whose two planes the masks are (the network's own when both are views of one,
-    as _mask_term_hip_autograd; anything else is interleaved by torch.stack)."""
-    base = getattr(mask_A, "_base", None)
-    dense, acc = [], 2
-    for n_i in reversed(mask_A.shape):
-        dense.insert(0, acc)
-        acc *= n_i
-    if (base is not None and getattr(mask_B, "_base", None) is base and base.dtype == torch.float32 and base.is_contiguous()
-            and base.numel() == 2 * mask_A.numel() and mask_A.stride() == mask_B.stride() == tuple(dense)
-            and mask_A.storage_offset() == base.storage_offset() and mask_B.storage_offset() == base.storage_offset() + 1):
-        return base
-    return torch.stack([mask_A.float(), mask_B.float()], -1)
-
-
 def _phase_terms_launch(masks, pa, pb, mag, s1, s2, q1, q2):
-    from .hip import get_lib
-    lib = get_lib()
-    B = mag.shape[0]
-    TF = mag[0].numel()
-    dev = mag.device
+    lib = _lib()
+    (B, TF), dev = _rows(mag), mag.device
     out_mask = torch.empty(B, device=dev, dtype=torch.float32)
     out_phase = torch.empty(B, device=dev, dtype=torch.float32)
     perm = torch.empty(B, device=dev, dtype=torch.int32)
-    ws = torch.empty(lib.loss_phase_workspace_bytes(B), dtype=torch.uint8, device=dev)
-    p = masks.data_ptr()
-    lib.loss_phase(p, p + 4, 2 * TF, 2, mag.data_ptr(), s1.data_ptr(), s2.data_ptr(), pa.data_ptr(), pb.data_ptr(), q1.data_ptr(),
+    ws = _ws(lib.loss_phase_workspace_bytes(B), dev)
+    lib.loss_phase(*_two_planes(masks), mag.data_ptr(), s1.data_ptr(), s2.data_ptr(), pa.data_ptr(), pb.data_ptr(), q1.data_ptr(),
                    q2.data_ptr(), B, TF, out_mask.data_ptr(), out_phase.data_ptr(), perm.data_ptr(), ws.data_ptr(), ws.numel(),
-                   torch.cuda.current_stream().cuda_stream)
+                   _stream())
     return out_mask, out_phase, perm
 
 
@@ -600,23 +580,18 @@ class _PhaseTermsHip(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_mask, g_phase):
-        from .hip import get_lib
         masks, pa, pb, mag, s1, s2, q1, q2, perm = ctx.saved_tensors
-        B = mag.shape[0]
-        TF = mag[0].numel()
         d, dpa, dpb = torch.empty_like(masks), torch.empty_like(pa), torch.empty_like(pb)
-        g_mask, g_phase = g_mask.float().contiguous(), g_phase.float().contiguous()
-        p, q = masks.data_ptr(), d.data_ptr()
-        get_lib().loss_phase_grad(p, p + 4, 2 * TF, 2, mag.data_ptr(), s1.data_ptr(), s2.data_ptr(), pa.data_ptr(), pb.data_ptr(),
-                                  q1.data_ptr(), q2.data_ptr(), B, TF, g_mask.data_ptr(), g_phase.data_ptr(), perm.data_ptr(),
-                                  q, q + 4, 2 * TF, 2, dpa.data_ptr(), dpb.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        g_mask, g_phase = _grad_in(g_mask), _grad_in(g_phase)
+        _lib().loss_phase_grad(*_two_planes(masks), mag.data_ptr(), s1.data_ptr(), s2.data_ptr(), pa.data_ptr(), pb.data_ptr(),
+                               q1.data_ptr(), q2.data_ptr(), *_rows(mag), g_mask.data_ptr(), g_phase.data_ptr(),
+                               perm.data_ptr(), *_two_planes(d), dpa.data_ptr(), dpb.data_ptr(), _stream())
         return d, dpa, dpb, None, None, None, None, None
 
 
 def _phase_terms_hip(mask_A, mask_B, phase_A, phase_B, mag_mix, mag_s1, mag_s2, phase_s1, phase_s2, needs_grad):
-    lab = lambda t: t.detach().float().contiguous()
-    labels = [lab(t) for t in (mag_mix, mag_s1, mag_s2, phase_s1, phase_s2)]
-    masks = _phase_interleaved_masks(mask_A, mask_B)
+    labels = [_lab(t) for t in (mag_mix, mag_s1, mag_s2, phase_s1, phase_s2)]
+    masks = _planes_base((mask_A, mask_B))
     pa, pb = phase_A.float().contiguous(), phase_B.float().contiguous()
     if needs_grad:
         return _PhaseTermsHip.apply(masks, pa, pb, *labels)
@@ -765,7 +740,7 @@ def _pit_rows(t):
 def _pit_stacked_base(ests):
     """The (k, N, S) tensor whose k slices the estimates are (what ConvTasNet's training forward returns), or None.  The node is
     then applied to that tensor itself: the gradient (k, N, S) goes to it as it is written, not through k select views whose
-    gradients autograd would scatter into zeros and add (as _mask_term_hip_autograd does for the chimera masks)."""
+    gradients autograd would scatter into zeros and add (as _planes_base does for the mask networks)."""
     base = getattr(ests[0], "_base", None)
     k, (N, S) = len(ests), ests[0].shape
     if base is None or not base.requires_grad or base.dtype != torch.float32 or not base.is_contiguous():
@@ -788,8 +763,7 @@ class _SisnrPitHip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, k, lengths, stacked, *ts):
-        from .hip import get_lib
-        lib = get_lib()
+        lib = _lib()
         if stacked:
             base, refs = ts[0], ts[1:]
             ests = [base[i] for i in range(k)]
@@ -802,12 +776,12 @@ class _SisnrPitHip(torch.autograd.Function):
         est = lib.sisnr_signals([e.data_ptr() for e, _ in ests], [st for _, st in ests])
         ref = lib.sisnr_signals([r.data_ptr() for r, _ in refs], [st for _, st in refs])
         nbytes = lib.sisnr_pit_workspace_bytes(N, k)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # owned by the graph: the backward reads the coefficients in it
+        ws = _ws(nbytes, dev)                    # owned by the graph: the backward reads the coefficients in it
         value = torch.empty(N, device=dev, dtype=torch.float32)
         total = torch.empty((), device=dev, dtype=torch.float32)
         perm = torch.empty(N, device=dev, dtype=torch.int32)
-        lib.sisnr_pit(est, ref, k, N, S, None if lengths is None else lengths.data_ptr(), value.data_ptr(), perm.data_ptr(),
-                      total.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
+        lib.sisnr_pit(est, ref, k, N, S, _ptr(lengths), value.data_ptr(), perm.data_ptr(), total.data_ptr(), ws.data_ptr(), nbytes,
+                      _stream())
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(perm)
         ctx.sig = ([e for e, _ in ests], [r for r, _ in refs], est, ref, ws, lengths)
@@ -817,17 +791,14 @@ class _SisnrPitHip(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_value, g_total, _g_perm):
-        from .hip import get_lib
         k, N, S, stacked, n_in = ctx.geom
         if g_value is None and g_total is None:
             return (None,) * (3 + n_in)
         ests, refs, est, ref, ws, lengths = ctx.sig
-        f32 = lambda g: None if g is None else g.float().contiguous()
-        g_value, g_total = f32(g_value), f32(g_total)
+        g_value, g_total = _grad_in(g_value), _grad_in(g_total)
         d = torch.empty(k, N, S, device=ws.device, dtype=torch.float32)
-        get_lib().sisnr_pit_backward(est, ref, k, N, S, None if lengths is None else lengths.data_ptr(),
-                                     None if g_value is None else g_value.data_ptr(), None if g_total is None else g_total.data_ptr(),
-                                     d.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+        _lib().sisnr_pit_backward(est, ref, k, N, S, _ptr(lengths), _ptr(g_value), _ptr(g_total), d.data_ptr(), ws.data_ptr(),
+                                  ws.numel(), _stream())
         grads = [d] if stacked else [d[i] for i in range(k)]
         return (None, None, None, *grads, *([None] * (n_in - len(grads))))
 
@@ -881,17 +852,15 @@ def _wa_ref_rows(ref, n):
 
 
 def _wa_pit_launch(est, ref, lengths):
-    from .hip import get_lib
-    lib = get_lib()
+    lib = _lib()
     B, C, n = est.shape
     dev = est.device
     nbytes = lib.wa_pit_workspace_bytes(B, C)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _ws(nbytes, dev)
     value = torch.empty(B, device=dev, dtype=torch.float32)
     perm = torch.empty(B, device=dev, dtype=torch.int32)
     lib.wa_pit(est.data_ptr(), ref.data_ptr(), ref.stride(0) if B > 1 else C * n, ref.stride(1) if C > 1 else n, B, C, n,
-               None if lengths is None else lengths.data_ptr(), value.data_ptr(), perm.data_ptr(), None, ws.data_ptr(), nbytes,
-               torch.cuda.current_stream().cuda_stream)
+               _ptr(lengths), value.data_ptr(), perm.data_ptr(), None, ws.data_ptr(), nbytes, _stream())
     return value, perm, ws
 
 
@@ -911,14 +880,12 @@ class _WaPitHip(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_value, _g_perm):
-        from .hip import get_lib
         est, ref, lengths, ws = ctx.sig
         B, C, n = est.shape
-        g_value = g_value.float().contiguous()
+        g_value = _grad_in(g_value)
         d = torch.empty_like(est)
-        get_lib().wa_pit_backward(est.data_ptr(), ref.data_ptr(), ref.stride(0) if B > 1 else C * n, ref.stride(1) if C > 1 else n,
-                                  B, C, n, None if lengths is None else lengths.data_ptr(), g_value.data_ptr(), None, d.data_ptr(),
-                                  ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+        _lib().wa_pit_backward(est.data_ptr(), ref.data_ptr(), ref.stride(0) if B > 1 else C * n, ref.stride(1) if C > 1 else n,
+                               B, C, n, _ptr(lengths), g_value.data_ptr(), None, d.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         return d, None, None
 
 
@@ -997,7 +964,7 @@ def loss_wa(output, label, hop_size=64, frames=None, lengths=None, kind="chimera
     if kind == "enhance":
         est = features.mag_istft(stft_ri, masks[0], hop_size, n, **rag)
     else:
-        base = _upit_masks_base(masks)               # the network's own interleaved buffer when the masks are its planes
+        base = _planes_base(masks)               # the network's own interleaved buffer when the masks are its planes
         if kind == "phase":
             for p in output[3:]:
                 if tuple(p.shape) != (B, T, F, 2):
