@@ -1,4 +1,5 @@
-// N1 deep-clustering loss value and N4 batch SI-SDR (part of onssen_hip.hip).
+// N1 deep-clustering loss, value and gradient, and the fused way from that gradient to fc_dc's GEMM operands: their kernels and
+// their C ABI entries (part of onssen_hip.hip).
 // =================================================================================================
 // N1 (forward half): deep-clustering loss value, onssen/loss/loss_dc.py:6-44 with loss_util.py:4-11.
 // Per utterance b: z_r = [ s_r * V_r (D) | Y_r (C) ], s_r = sum_c Y_r[c] (0 on silent bins), weight w_r^2 =
@@ -20,7 +21,7 @@ __global__ __launch_bounds__(256) void loss_dc_partial_kernel(const float* __res
   __shared__ __attribute__((aligned(16))) float q[RT][QS];      // sqrt(mag_r) * z_r
   __shared__ float msum[256];
   const int tid = threadIdx.x, blk = blockIdx.x, b = blockIdx.y;
-  const int Z = D + C, nout = Z * Z, ZB = (Z + 3) / 4;
+  const int Z = D + C, ZB = (Z + 3) / 4;
   const int rows_per = (TF + NBLK - 1) / NBLK, r0 = blk * rows_per, r1 = r0 + rows_per < TF ? r0 + rows_per : TF;
   // thread task (i, jb): outputs G[i][4 jb .. 4 jb + 3] -- one 4-byte and one 16-byte LDS read per row and FOUR multiply-adds
   // (one output per thread read two values per multiply-add and was bound by the LDS, not by HBM)
@@ -73,7 +74,6 @@ __global__ __launch_bounds__(256) void loss_dc_partial_kernel(const float* __res
         if (4 * tj + c < Z) dst[ti * Z + 4 * tj + c] = acc[s2][c];
     }
   }
-  (void)nout;
   msum[tid] = mtot;
   __syncthreads();
   for (int sft = 128; sft > 0; sft >>= 1) {
@@ -454,118 +454,69 @@ __global__ __launch_bounds__(256) void dc_head_grad_images_kernel(const float* _
 }
 
 // =================================================================================================
-// N4: batch SI-SDR with best permutation, onssen/evaluate/sdr.py:11-87 (calc_sdr_torch + batch_SDR_torch).
-// Everything the metric needs per utterance is the Gram matrix of the 2C zero-mean (optionally masked) signals
-// [est_0..est_{C-1}, org_0..org_{C-1}]: pass 1 sums the signals (means), pass 2 the centred products, a last
-// workgroup per utterance forms the C x C SDR table and scans the C! permutations in the reference's
-// (lexicographic) order.  The separated waveforms never leave the device.
-// The reference sums (est - scale*org)^2 directly; from a Gram matrix the residual power is ee - 2 s eo + s^2 oo, which
-// cancels: with fp32 sums it is wrong by 0.1 dB at 50 dB SDR and negative (NaN) from ~70 dB.  The Gram matrix, the
-// means and the table are therefore accumulated and evaluated in fp64 (good to ~140 dB, the resolution of the fp32 inputs).
+// C ABI
 // =================================================================================================
-namespace sdr {
-constexpr int NBLK = 32, CMAX = 4, SMAX = 2 * CMAX, TS = 256;
-constexpr int PSTRIDE = SMAX * SMAX + SMAX;     // per (b, block): Gram then sums
-}  // namespace sdr
+extern "C" {
 
-template <int PASS>
-__global__ __launch_bounds__(256) void sdr_partial_kernel(const float* __restrict__ est, const float* __restrict__ org,
-                                                          const float* __restrict__ mask, int C, int n,
-                                                          const double* __restrict__ means, double* __restrict__ partial,
-                                                          const int* __restrict__ lengths) {
-  using namespace sdr;
-  __shared__ float tile[SMAX][TS + 1];
-  const int tid = threadIdx.x, blk = blockIdx.x, b = blockIdx.y, S = 2 * C;
-  // ragged batch: row b holds lengths[b] <= n samples of its own (rows keep the stride n; the padding takes no part)
-  const int nb = lengths ? lengths[b] : n;
-  const int per = (nb + NBLK - 1) / NBLK, s0 = blk * per, s1 = s0 + per < nb ? s0 + per : nb;
-  float mu[SMAX];
-#pragma unroll
-  for (int k = 0; k < SMAX; ++k) mu[k] = (PASS == 1 && k < S) ? (float)means[b * SMAX + k] : 0.0f;   // the reference subtracts an fp32 mean
-  double acc = 0.0;                              // PASS 0: thread k < S sums signal k; PASS 1: thread o < S*S -> G[o/S][o%S]
-  for (int t0 = s0; t0 < s1; t0 += TS) {
-    const int nt = s1 - t0 < TS ? s1 - t0 : TS;
-    __syncthreads();
-    for (int e = tid; e < S * TS; e += 256) {
-      const int k = e / TS, i = e % TS;
-      float v = 0.0f;
-      if (i < nt) {
-        const float* src = (k < C ? est + ((long)b * C + k) * n : org + ((long)b * C + (k - C)) * n);
-        v = src[t0 + i];
-        if (PASS == 1) {
-          v -= mu[k];
-          if (mask) v *= mask[(long)b * n + t0 + i];
-        }
-      }
-      tile[k][i] = v;
-    }
-    __syncthreads();
-    if (PASS == 0) {
-      if (tid < S) for (int i = 0; i < nt; ++i) acc += tile[tid][i];
-    } else if (tid < S * S) {
-      const int k = tid / S, l = tid % S;
-      for (int i = 0; i < nt; ++i) acc += (double)tile[k][i] * (double)tile[l][i];
-    }
-  }
-  double* dst = partial + ((long)b * NBLK + blk) * PSTRIDE;
-  if (PASS == 0) {
-    if (tid < S) dst[SMAX * SMAX + tid] = acc;
-  } else if (tid < S * S) {
-    dst[tid] = acc;
-  }
+size_t onssen_loss_dc_workspace_bytes(int B) {   // partial Grams + (gradient pass) one M matrix and sum(mag) per utterance
+  return B > 0 ? (size_t)B * (lossdc::NBLK + 1) * (lossdc::ZMAX * lossdc::ZMAX + 1) * sizeof(float) : 0;
+}
+int onssen_loss_dc_f32(const float* emb, const float* one_hot, const float* mag, int B, int TF, int D, int C,
+                       float* per_utt, float* total_mag, void* ws, size_t ws_bytes, void* stream) {
+  if (!emb || !one_hot || !mag || !per_utt || !total_mag || !ws || B <= 0 || TF <= 0 || D <= 0 || C <= 0 ||
+      D + C > lossdc::ZMAX)
+    return ONSSEN_E_ARG;
+  if (ws_bytes < onssen_loss_dc_workspace_bytes(B)) return ONSSEN_E_WORKSPACE;
+  ONSSEN_CLEAR_ERROR();
+  hipStream_t st = (hipStream_t)stream;
+  if (D + C <= 32)
+    hipLaunchKernelGGL(loss_dc_partial_mfma_kernel, dim3(lossdc::NBLK, (unsigned)B), dim3(256), 0, st, emb, one_hot, mag, TF, D, C,
+                       (float*)ws);
+  else
+    hipLaunchKernelGGL(loss_dc_partial_kernel, dim3(lossdc::NBLK, (unsigned)B), dim3(256), 0, st, emb, one_hot, mag, TF, D, C,
+                       (float*)ws);
+  hipLaunchKernelGGL(loss_dc_final_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)ws, D, C, per_utt, total_mag);
+  ONSSEN_LAUNCH_CHECK();
+  return ONSSEN_OK;
 }
 
-__global__ void sdr_means_kernel(const double* __restrict__ partial, int C, int n, double* __restrict__ means,
-                                 const int* __restrict__ lengths) {
-  using namespace sdr;
-  const int b = blockIdx.x, k = threadIdx.x;
-  if (lengths) n = lengths[b];
-  if (k < 2 * C) {
-    double s = 0.0;
-    for (int blk = 0; blk < NBLK; ++blk) s += partial[((long)b * NBLK + blk) * PSTRIDE + SMAX * SMAX + k];
-    means[b * SMAX + k] = s / n;
-  }
+int onssen_dc_head_grad_images_f32(const float* emb, const float* inv_norm, const float* one_hot, const float* mag, int B, int T,
+                                   int F, int D, int C, float eps, const float* g_per_utt, void* ws, size_t ws_bytes,
+                                   uint16_t* img_rows, uint16_t* img_t, float* colsum, void* stream) {
+  if (!emb || !inv_norm || !one_hot || !mag || !g_per_utt || !ws || !img_rows || !colsum || B <= 0 || F <= 0 || C <= 0 ||
+      C > 4 || D != 20 || T < 32 || !(eps > 0.0f) || (long)B * T > 0x7fffffffL / 64)
+    return ONSSEN_E_ARG;
+  if (!aligned16(emb) || !aligned16(img_rows) || (img_t && !aligned16(img_t))) return ONSSEN_E_ALIGN;
+  if (ws_bytes < onssen_loss_dc_workspace_bytes(B)) return ONSSEN_E_WORKSPACE;
+  ONSSEN_CLEAR_ERROR();
+  hipStream_t st = (hipStream_t)stream;
+  float* gm = (float*)ws + (size_t)B * lossdc::NBLK * (lossdc::ZMAX * lossdc::ZMAX + 1);
+  hipLaunchKernelGGL(loss_dc_gradm_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)ws, D, C, gm);
+  const dim3 grid((unsigned)ceil_div(F, 8), (unsigned)ceil_div(B * T, 32));
+  hipLaunchKernelGGL(dc_head_grad_images_kernel, grid, dim3(256), 0, st, emb, inv_norm, one_hot, mag, (const float*)gm, g_per_utt, B, T,
+                     F, C, eps, img_rows, img_t, colsum);
+  ONSSEN_LAUNCH_CHECK();
+  return ONSSEN_OK;
 }
 
-__global__ void sdr_final_kernel(const double* __restrict__ partial, int C, float* __restrict__ sdr_out, int* __restrict__ perm_out) {
-  using namespace sdr;
-  __shared__ double G[SMAX][SMAX];
-  __shared__ float tab[CMAX][CMAX];
-  const int b = blockIdx.x, tid = threadIdx.x, S = 2 * C;
-  if (tid < S * S) {
-    double s = 0.0;
-    for (int blk = 0; blk < NBLK; ++blk) s += partial[((long)b * NBLK + blk) * PSTRIDE + tid];
-    G[tid / S][tid % S] = s;
-  }
-  __syncthreads();
-  if (tid < C * C) {       // SDR[i][j] of estimate i against source j (sdr.py:23-33)
-    const int i = tid / C, j = tid % C;
-    const double oo = G[C + j][C + j], ee = G[i][i], eo = G[i][C + j];
-    const double scale = eo / (oo + 1e-8);
-    const double true_p = scale * scale * oo + 1e-8;
-    const double res = ee - 2.0 * scale * eo + scale * scale * oo;        // >= 0 up to rounding
-    const double res_p = (res > 0.0 ? res : 0.0) + 1e-8;
-    tab[i][j] = (float)(10.0 * log10(true_p) - 10.0 * log10(res_p));
-  }
-  __syncthreads();
-  if (tid == 0) {          // permutations in lexicographic order (sorted(set(permutations(range(C)))), sdr.py:74)
-    int perm[CMAX], best_idx = 0, idx = 0;
-    for (int k = 0; k < C; ++k) perm[k] = k;
-    float best = -3.0e38f;
-    for (;;) {
-      float v = 0.0f;
-      for (int k = 0; k < C; ++k) v += tab[k][perm[k]];
-      if (v > best) { best = v; best_idx = idx; }      // torch.max keeps the first maximum
-      ++idx;
-      int a = C - 2;                                   // next lexicographic permutation
-      while (a >= 0 && perm[a] > perm[a + 1]) --a;
-      if (a < 0) break;
-      int c = C - 1;
-      while (perm[c] < perm[a]) --c;
-      int t = perm[a]; perm[a] = perm[c]; perm[c] = t;
-      for (int l = a + 1, r = C - 1; l < r; ++l, --r) { t = perm[l]; perm[l] = perm[r]; perm[r] = t; }
-    }
-    sdr_out[b] = best / (float)C;
-    if (perm_out) perm_out[b] = best_idx;
-  }
+int onssen_loss_dc_grad_f32(const float* emb, const float* one_hot, const float* mag, int B, int TF, int D, int C,
+                            const float* g_per_utt, float* d_emb, void* ws, size_t ws_bytes, void* stream) {
+  if (!emb || !one_hot || !mag || !g_per_utt || !d_emb || !ws || B <= 0 || TF <= 0 || D <= 0 || C <= 0 || C > 4 ||
+      D + C > lossdc::ZMAX)
+    return ONSSEN_E_ARG;
+  if (ws_bytes < onssen_loss_dc_workspace_bytes(B)) return ONSSEN_E_WORKSPACE;
+  ONSSEN_CLEAR_ERROR();
+  hipStream_t st = (hipStream_t)stream;
+  float* gm = (float*)ws + (size_t)B * lossdc::NBLK * (lossdc::ZMAX * lossdc::ZMAX + 1);
+  hipLaunchKernelGGL(loss_dc_gradm_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)ws, D, C, gm);
+  const int nb = ceil_div(TF, 256) > 64 ? 64 : ceil_div(TF, 256);
+  const dim3 grid((unsigned)nb, (unsigned)B);
+  if (D == 20 && aligned16(emb) && aligned16(d_emb))
+    hipLaunchKernelGGL((loss_dc_grad_kernel<20>), grid, dim3(256), 0, st, emb, one_hot, mag, gm, g_per_utt, TF, D, C, d_emb);
+  else
+    hipLaunchKernelGGL((loss_dc_grad_kernel<0>), grid, dim3(256), 0, st, emb, one_hot, mag, gm, g_per_utt, TF, D, C, d_emb);
+  ONSSEN_LAUNCH_CHECK();
+  return ONSSEN_OK;
 }
+
+}  // extern "C"

@@ -9,9 +9,9 @@
 //   sisnr_partial_kernel  grid (chunks, rows): a workgroup reads its chunk of all 2k signals ONCE and writes fp64 partial moments
 //   sisnr_final_kernel    one workgroup per row: partials merged in chunk order, the k x k table, the permutation scan, V_b, and
 //                         per (row, estimate) the three coefficients of the gradient -- all fp64
-//   sisnr_total_kernel    the scalar loss, a fixed-order sum over the rows
+//   pit_total_kernel      the scalar loss, a fixed-order sum over the rows (pit.inc)
 //   sisnr_backward_kernel d_est[i][b][t] = A x_i[b,t] + B s_p(i)[b,t] + C, evaluated in fp64 and rounded once
-// The cancellation note of the SDR section of loss_sdr.inc applies: n^2 = |x~|^2 - (D^2 / E)(1 + eps / E) from a Gram matrix
+// The cancellation note of batch_sdr.inc applies: n^2 = |x~|^2 - (D^2 / E)(1 + eps / E) from a Gram matrix
 // cancels, so sums, table and coefficients are fp64 and there is no fp32 log10f.  The moments are taken of x - x[0] and
 // s - s[0] (the row's first sample as pivot; centred moments do not depend on it): a constant signal has exactly zero moments
 // whatever its value, and a DC offset costs no digits.
@@ -26,9 +26,10 @@
 // which lies in span{x, s, 1}:  A = -K cN,  B = K (cT + cN a (1 + eps / E)),  C = -(A mean(x) + B mean(s)).
 // =================================================================================================
 namespace sisnr {
-constexpr int CMAX = 4;                         // speakers, as sdr::CMAX
-constexpr int NCH = 64;                         // chunks of a row at most
-constexpr int CHMIN = 512;                      // samples of a chunk at least
+using pit::CMAX;
+using pit::NCH;
+using pit::row_len;
+constexpr int CHMIN = 512;                      // samples of a chunk at least (pit::chunk_len)
 constexpr int NM = 4 * CMAX + CMAX * CMAX;      // moments per (row, chunk): sums (est | ref), squared norms (est | ref), products
 constexpr int NCOEF = 4;                        // A, B, C per (row, estimate), one spare
 constexpr double EPS = 1e-8;
@@ -37,15 +38,6 @@ struct Sig {                                    // the 2k signals: row b of esti
   const float* ref[CMAX];
   long es[CMAX], rs[CMAX];
 };
-// samples one workgroup takes of a row of len samples: a function of the row's own length (a multiple of 4)
-__host__ __device__ inline int chunk_len(int len) {
-  const int per = ((len + NCH - 1) / NCH + 3) & ~3;
-  return per < CHMIN ? CHMIN : per;
-}
-__device__ __forceinline__ int row_len(const int* lengths, int b, int S) {
-  const int l = lengths ? lengths[b] : S;
-  return l < 1 ? 1 : l > S ? S : l;               // a device-side length cannot be refused by the host: it is clamped
-}
 // p[i] without indexing the kernel-argument block with a run-time value
 template <class T>
 __device__ __forceinline__ T pick(const T (&p)[CMAX], int i) {
@@ -62,25 +54,13 @@ __device__ __forceinline__ bool slot_used(int slot, int K) {
 }
 }  // namespace sisnr
 
-// four consecutive samples of a row from t (fewer at the row's end): one 16-byte load where the row allows it
-template <bool VEC>
-__device__ __forceinline__ void sisnr_load4(const float* __restrict__ p, int t, int nv, float (&v)[4]) {
-  if (VEC && nv == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p + t);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[t + j] : 0.0f;
-  }
-}
-
 template <int K, bool VEC>
 __global__ __launch_bounds__(256) void sisnr_partial_kernel(sisnr::Sig sg, int S, const int* __restrict__ lengths,
                                                             double* __restrict__ partial) {
   using namespace sisnr;
   __shared__ double red[4][NM];
-  const int tid = threadIdx.x, b = blockIdx.y, wave = tid >> 6, lane = tid & 63;
-  const int len = row_len(lengths, b, S), per = chunk_len(len), c0 = (int)blockIdx.x * per;
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int len = row_len(lengths, b, S), per = pit::chunk_len(len, CHMIN), c0 = (int)blockIdx.x * per;
   if (c0 >= len) return;                           // (the whole workgroup) this row has fewer chunks than the longest
   const int c1 = c0 + per < len ? c0 + per : len;
   const float* xp[K];
@@ -105,8 +85,8 @@ __global__ __launch_bounds__(256) void sisnr_partial_kernel(sisnr::Sig sg, int S
     float xv[K][4], sv[K][4];
 #pragma unroll
     for (int i = 0; i < K; ++i) {
-      sisnr_load4<VEC>(xp[i], t, nv, xv[i]);
-      sisnr_load4<VEC>(sp[i], t, nv, sv[i]);
+      pit::load4(xp[i], t, nv, VEC, xv[i]);
+      pit::load4(sp[i], t, nv, VEC, sv[i]);
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -128,19 +108,13 @@ __global__ __launch_bounds__(256) void sisnr_partial_kernel(sisnr::Sig sg, int S
   }
 #pragma unroll
   for (int i = 0; i < K; ++i) {
-    const double a0 = tas::wave_sum_d(sx[i]), a1 = tas::wave_sum_d(ss[i]), a2 = tas::wave_sum_d(qx[i]), a3 = tas::wave_sum_d(qs[i]);
-    if (lane == 0) {
-      red[wave][i] = a0; red[wave][CMAX + i] = a1; red[wave][2 * CMAX + i] = a2; red[wave][3 * CMAX + i] = a3;
-    }
+    pit::wave_put(red, i, sx[i]); pit::wave_put(red, CMAX + i, ss[i]);                         // sums
+    pit::wave_put(red, 2 * CMAX + i, qx[i]); pit::wave_put(red, 3 * CMAX + i, qs[i]);         // squared norms
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
-      const double a4 = tas::wave_sum_d(xs[i][j]);
-      if (lane == 0) red[wave][4 * CMAX + i * CMAX + j] = a4;
-    }
+    for (int j = 0; j < K; ++j) pit::wave_put(red, 4 * CMAX + i * CMAX + j, xs[i][j]);
   }
   __syncthreads();
-  if (tid < NM && slot_used(tid, K))
-    partial[((long)b * NCH + blockIdx.x) * NM + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+  if (tid < NM && slot_used(tid, K)) partial[((long)b * NCH + blockIdx.x) * NM + tid] = pit::block_sum(red, tid);
 }
 
 // One workgroup per row: the moments, the k x k table with the gradient's coefficients, the permutation scan.
@@ -151,9 +125,8 @@ __global__ __launch_bounds__(64) void sisnr_final_kernel(sisnr::Sig sg, int K, i
   using namespace sisnr;
   __shared__ double m[NM];
   __shared__ double tab[CMAX][CMAX], cA[CMAX][CMAX], cB[CMAX][CMAX], cC[CMAX][CMAX];
-  __shared__ int perm[CMAX], bperm[CMAX];
   const int tid = threadIdx.x, b = blockIdx.x;
-  const int len = row_len(lengths, b, S), per = chunk_len(len), nch = (len + per - 1) / per;
+  const int len = row_len(lengths, b, S), per = pit::chunk_len(len, CHMIN), nch = (len + per - 1) / per;
   if (tid < NM) {
     double s = 0.0;
     if (slot_used(tid, K))
@@ -186,44 +159,25 @@ __global__ __launch_bounds__(64) void sisnr_final_kernel(sisnr::Sig sg, int K, i
     cC[i][j] = -(A * (px + mx) + B * (ps + ms));
   }
   __syncthreads();
-  if (tid == 0) {          // permutations in lexicographic order, the first maximum wins (as sdr_final_kernel)
-    int best_idx = 0, idx = 0;
-    for (int q = 0; q < K; ++q) perm[q] = bperm[q] = q;
+  if (tid == 0) {          // the first maximum of the MEAN wins: sums that round to one quotient tie
+    pit::Perms e(K), win = e;
     double best = 0.0;
-    for (;;) {
+    do {
       double v = 0.0;
-      for (int q = 0; q < K; ++q) v += tab[q][perm[q]];
+      for (int q = 0; q < K; ++q) v += tab[q][e.p(q)];
       v /= (double)K;
-      if (idx == 0 || v > best) {
-        best = v; best_idx = idx;
-        for (int q = 0; q < K; ++q) bperm[q] = perm[q];
-      }
-      ++idx;
-      int p = K - 2;                                   // next lexicographic permutation
-      while (p >= 0 && perm[p] > perm[p + 1]) --p;
-      if (p < 0) break;
-      int c = K - 1;
-      while (perm[c] < perm[p]) --c;
-      int t = perm[p]; perm[p] = perm[c]; perm[c] = t;
-      for (int l = p + 1, r = K - 1; l < r; ++l, --r) { t = perm[l]; perm[l] = perm[r]; perm[r] = t; }
-    }
+      if (e.idx == 0 || v > best) { best = v; win = e; }
+    } while (e.next());
     value[b] = (float)best;
     vals[b] = best;
-    if (perm_out) perm_out[b] = best_idx;
+    if (perm_out) perm_out[b] = win.idx;
     for (int q = 0; q < K; ++q) {
-      const int j = bperm[q];
+      const int j = win.p(q);
       double* dst = coef + ((long)b * CMAX + q) * NCOEF;
       dst[0] = cA[q][j] / (double)K; dst[1] = cB[q][j] / (double)K; dst[2] = cC[q][j] / (double)K; dst[3] = 0.0;
       pj[b * CMAX + q] = j;
     }
   }
-}
-
-__global__ __launch_bounds__(64) void sisnr_total_kernel(const double* __restrict__ vals, int N, float* __restrict__ total) {
-  double s = 0.0;
-  for (int b = threadIdx.x; b < N; b += 64) s += vals[b];
-  s = tas::wave_sum_d(s);
-  if (threadIdx.x == 0) total[0] = (float)(-s / (double)N);
 }
 
 // d_est (k, N, S) contiguous, written once: the chosen assignment's A x + B s + C inside the row's length, zero beyond it.
@@ -238,42 +192,33 @@ __global__ __launch_bounds__(256) void sisnr_backward_kernel(sisnr::Sig sg, int 
   const long t = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (t >= S) return;
   const int len = row_len(lengths, b, S), j = pj[b * CMAX + i];
-  const double w = (g_value ? (double)g_value[b] : 0.0) - (g_total ? (double)g_total[0] / (double)N : 0.0);
+  const double w = pit::row_weight(g_value, g_total, b, N, -1.0);
   const double* cf = coef + ((long)b * CMAX + i) * NCOEF;
   const double A = w * cf[0], B = w * cf[1], C = w * cf[2];
   const float* x = pick(sg.est, i) + (long)b * pick(sg.es, i);
   const float* s = pick(sg.ref, j) + (long)b * pick(sg.rs, j);
   float* out = d_est + ((long)i * N + b) * S;
-  const int nv = len - t >= 4 ? 4 : len - t > 0 ? (int)(len - t) : 0;       // samples inside the row's length
+  const int nv = pit::inside4(len, t);
   float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   if (nv > 0) {
     float xv[4], sv[4];
-    sisnr_load4<VIN>(x, (int)t, nv, xv);
-    sisnr_load4<VIN>(s, (int)t, nv, sv);
+    pit::load4(x, (int)t, nv, VIN, xv);
+    pit::load4(s, (int)t, nv, VIN, sv);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
       if (e < nv) o[e] = (float)(A * (double)xv[e] + B * (double)sv[e] + C);
   }
-  if (VOUT) {
-    *reinterpret_cast<float4*>(out + t) = make_float4(o[0], o[1], o[2], o[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (t + e < S) out[t + e] = o[e];
-  }
+  pit::store4(out, t, S, VOUT, o);
 }
 
 // =================================================================================================
 // C ABI
 // =================================================================================================
-extern "C" size_t onssen_sisnr_pit_workspace_bytes(int N, int k);
-
 namespace sisnr {
 struct Plan {
   Sig sg;
   bool vec;             // every row of every signal starts on a 16-byte boundary
-  double *partial, *vals, *coef;
-  int* pj;
+  pit::Ws w;            // extra: the coefficients
 };
 // everything both entries refuse, before anything is launched or written
 static int plan(const float* const* est_host, const int64_t* est_stride_host, const float* const* ref_host,
@@ -290,22 +235,7 @@ static int plan(const float* const* est_host, const int64_t* est_stride_host, co
     p->vec = p->vec && aligned16(est_host[q]) && aligned16(ref_host[q]) &&
              (N == 1 || (est_stride_host[q] % 4 == 0 && ref_stride_host[q] % 4 == 0));
   }
-  if (ws_bytes < onssen_sisnr_pit_workspace_bytes(N, k)) return ONSSEN_E_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(ws) & 7u) != 0) return ONSSEN_E_ALIGN;
-  p->partial = (double*)ws;
-  p->vals = p->partial + (size_t)N * NCH * NM;
-  p->coef = p->vals + N;
-  p->pj = (int*)(p->coef + (size_t)N * CMAX * NCOEF);
-  return ONSSEN_OK;
-}
-template <bool VEC>
-static void launch_partial(const Plan& p, int k, dim3 grid, hipStream_t st, int S, const int* lengths) {
-  switch (k) {
-    case 1: hipLaunchKernelGGL((sisnr_partial_kernel<1, VEC>), grid, dim3(256), 0, st, p.sg, S, lengths, p.partial); break;
-    case 2: hipLaunchKernelGGL((sisnr_partial_kernel<2, VEC>), grid, dim3(256), 0, st, p.sg, S, lengths, p.partial); break;
-    case 3: hipLaunchKernelGGL((sisnr_partial_kernel<3, VEC>), grid, dim3(256), 0, st, p.sg, S, lengths, p.partial); break;
-    default: hipLaunchKernelGGL((sisnr_partial_kernel<4, VEC>), grid, dim3(256), 0, st, p.sg, S, lengths, p.partial); break;
-  }
+  return pit::carve(ws, ws_bytes, N, NM, CMAX * NCOEF, &p->w);
 }
 }  // namespace sisnr
 
@@ -314,7 +244,7 @@ extern "C" {
 size_t onssen_sisnr_pit_workspace_bytes(int N, int k) {
   using namespace sisnr;
   if (N < 1 || N > 65535 || k < 1 || k > CMAX) return 0;
-  return ((size_t)N * NCH * NM + (size_t)N + (size_t)N * CMAX * NCOEF) * sizeof(double) + (size_t)N * CMAX * sizeof(int32_t);
+  return pit::ws_bytes(N, NM, CMAX * NCOEF);
 }
 
 int onssen_sisnr_pit_f32(const float* const* est_host, const int64_t* est_stride_host, const float* const* ref_host,
@@ -327,14 +257,14 @@ int onssen_sisnr_pit_f32(const float* const* est_host, const int64_t* est_stride
   if (rc != ONSSEN_OK) return rc;
   ONSSEN_CLEAR_ERROR();
   hipStream_t st = (hipStream_t)stream;
-  // chunks of the longest possible row; a shorter row has no more of them (chunk_len)
-  const int nch = S >= NCH * CHMIN ? NCH : ceil_div(S, CHMIN);
-  const dim3 grid((unsigned)nch, (unsigned)N);
-  if (p.vec) launch_partial<true>(p, k, grid, st, S, (const int*)lengths);
-  else launch_partial<false>(p, k, grid, st, S, (const int*)lengths);
+  const dim3 grid((unsigned)pit::chunks(S, CHMIN), (unsigned)N);
+  pit::with_k(k, [&](auto K) { pit::with_flag(p.vec, [&](auto VEC) {
+    hipLaunchKernelGGL((sisnr_partial_kernel<decltype(K)::value, decltype(VEC)::value>), grid, dim3(256), 0, st, p.sg, S,
+                       (const int*)lengths, p.w.partial);
+  }); });
   hipLaunchKernelGGL(sisnr_final_kernel, dim3((unsigned)N), dim3(64), 0, st, p.sg, k, S, (const int*)lengths,
-                     (const double*)p.partial, value, (int*)perm, p.vals, p.coef, p.pj);
-  if (total) hipLaunchKernelGGL(sisnr_total_kernel, dim3(1), dim3(64), 0, st, (const double*)p.vals, N, total);
+                     (const double*)p.w.partial, value, (int*)perm, p.w.vals, p.w.extra, p.w.pj);
+  if (total) hipLaunchKernelGGL(pit_total_kernel, dim3(1), dim3(64), 0, st, (const double*)p.w.vals, N, -1.0, total);
   ONSSEN_LAUNCH_CHECK();
   return ONSSEN_OK;
 }
@@ -351,15 +281,10 @@ int onssen_sisnr_pit_backward_f32(const float* const* est_host, const int64_t* e
   ONSSEN_CLEAR_ERROR();
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)ceil_div(S, 1024), (unsigned)N, (unsigned)k);
-  const bool vout = aligned16(d_est) && S % 4 == 0;
-#define ONSSEN_SISNR_BWD(VIN, VOUT)                                                                                          \
-  hipLaunchKernelGGL((sisnr_backward_kernel<VIN, VOUT>), grid, dim3(256), 0, st, p.sg, N, S, (const int*)lengths, g_value,  \
-                     g_total, (const double*)p.coef, (const int*)p.pj, d_est)
-  if (p.vec && vout) ONSSEN_SISNR_BWD(true, true);
-  else if (p.vec) ONSSEN_SISNR_BWD(true, false);
-  else if (vout) ONSSEN_SISNR_BWD(false, true);
-  else ONSSEN_SISNR_BWD(false, false);
-#undef ONSSEN_SISNR_BWD
+  pit::with_flags(p.vec, aligned16(d_est) && S % 4 == 0, [&](auto VIN, auto VOUT) {
+    hipLaunchKernelGGL((sisnr_backward_kernel<decltype(VIN)::value, decltype(VOUT)::value>), grid, dim3(256), 0, st, p.sg, N, S,
+                       (const int*)lengths, g_value, g_total, (const double*)p.w.extra, (const int*)p.w.pj, d_est);
+  });
   ONSSEN_LAUNCH_CHECK();
   return ONSSEN_OK;
 }

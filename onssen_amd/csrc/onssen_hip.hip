@@ -23,8 +23,10 @@
 //                       Lloyd iterations in one persistent launch with register-resident rows; launch-per-iteration fallback)
 //   kmeans_k.inc        kmeansk_* (the same back end for 2 .. 4 speakers: farthest-point initialisation, launch-per-iteration Lloyd,
 //                       K-channel masks)
-//   loss_sdr.inc        loss_dc_* (value and gradient), sdr_* (batch SI-SDR with best permutation, fp64 sums)
-//   loss_mask.inc       loss_mask_* (chimera mask term: value, winning assignment, gradient)
+//   pit.inc             shared by the time-domain PIT losses: row chunks, 4-float loads, the permutation enumerator, pit_total_kernel
+//   loss_dc.inc         loss_dc_* (deep-clustering loss: value and gradient), dc_head_grad_images_kernel (that gradient as fc_dc's operands)
+//   batch_sdr.inc       sdr_* (batch SI-SDR with best permutation, fp64 sums)
+//   loss_mask.inc      loss_mask_* (chimera mask term: value, winning assignment, gradient)
 //   loss_sisnr.inc      sisnr_* (Conv-TasNet's SI-SNR permutation-invariant training loss: value, assignment, gradient; fp64 moments)
 //   loss_phase.inc      loss_phase_* (phase_net's training loss: mask term and cosine phase term in one pass, assignment, gradient)
 //   enhance.inc         labels_enhance_kernel (|X|, |S|, cos of the phase difference in one pass), loss_enhance_* (the MSA / PSA
@@ -92,6 +94,18 @@ __device__ __forceinline__ s16x4 lds_read_tr16(const unsigned short* p) {
 }
 #endif
 
+// the sum of v over the 64 lanes of a wave, in every lane
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
 // hipGetLastError() is sticky per thread: other libraries' failed probes (e.g. a device query before
 // the runtime is initialised) linger.  Every ABI entry clears it first, then checks its own launches.
 #define ONSSEN_CLEAR_ERROR() ((void)hipGetLastError())
@@ -137,7 +151,9 @@ static unsigned& xcd_spin_limit() {
 #include "fft.inc"
 #include "misi.inc"       // MISI phase reconstruction: the half-step between two inverse transforms (estimates -> phase maps)
 #include "istft_bwd.inc"  // waveform-approximation training: the adjoint of mask_istft_kernel, all three modes
-#include "loss_sdr.inc"
+#include "pit.inc"        // permutation-invariant losses: the shared geometry, loads, permutation enumerator, sums and host helpers
+#include "loss_dc.inc"    // deep-clustering loss and its gradient: its kernels and its C ABI entries
+#include "batch_sdr.inc"  // batch SI-SDR with best permutation: its kernels and its C ABI entries
 #include "loss_mask.inc"  // chimera training: the mask-inference term (better of the two speaker assignments) and its gradient
 #include "wav_io.inc"      // host code: the batch RIFF reader of the file loader
 #include "optim.inc"
@@ -345,103 +361,6 @@ int onssen_head_pack_f32(const float* w, const float* b, int N, int H, int Hp, c
                      bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, w_p, b_p);
   ONSSEN_LAUNCH_CHECK();
   return ONSSEN_OK;
-}
-
-size_t onssen_loss_dc_workspace_bytes(int B) {   // partial Grams + (gradient pass) one M matrix and sum(mag) per utterance
-  return B > 0 ? (size_t)B * (lossdc::NBLK + 1) * (lossdc::ZMAX * lossdc::ZMAX + 1) * sizeof(float) : 0;
-}
-int onssen_loss_dc_f32(const float* emb, const float* one_hot, const float* mag, int B, int TF, int D, int C,
-                       float* per_utt, float* total_mag, void* ws, size_t ws_bytes, void* stream) {
-  if (!emb || !one_hot || !mag || !per_utt || !total_mag || !ws || B <= 0 || TF <= 0 || D <= 0 || C <= 0 ||
-      D + C > lossdc::ZMAX)
-    return ONSSEN_E_ARG;
-  if (ws_bytes < onssen_loss_dc_workspace_bytes(B)) return ONSSEN_E_WORKSPACE;
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  if (D + C <= 32)
-    hipLaunchKernelGGL(loss_dc_partial_mfma_kernel, dim3(lossdc::NBLK, (unsigned)B), dim3(256), 0, st, emb, one_hot, mag, TF, D, C,
-                       (float*)ws);
-  else
-    hipLaunchKernelGGL(loss_dc_partial_kernel, dim3(lossdc::NBLK, (unsigned)B), dim3(256), 0, st, emb, one_hot, mag, TF, D, C,
-                       (float*)ws);
-  hipLaunchKernelGGL(loss_dc_final_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)ws, D, C, per_utt, total_mag);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-
-int onssen_dc_head_grad_images_f32(const float* emb, const float* inv_norm, const float* one_hot, const float* mag, int B, int T,
-                                   int F, int D, int C, float eps, const float* g_per_utt, void* ws, size_t ws_bytes,
-                                   uint16_t* img_rows, uint16_t* img_t, float* colsum, void* stream) {
-  if (!emb || !inv_norm || !one_hot || !mag || !g_per_utt || !ws || !img_rows || !colsum || B <= 0 || F <= 0 || C <= 0 ||
-      C > 4 || D != 20 || T < 32 || !(eps > 0.0f) || (long)B * T > 0x7fffffffL / 64)
-    return ONSSEN_E_ARG;
-  if (!aligned16(emb) || !aligned16(img_rows) || (img_t && !aligned16(img_t))) return ONSSEN_E_ALIGN;
-  if (ws_bytes < onssen_loss_dc_workspace_bytes(B)) return ONSSEN_E_WORKSPACE;
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  float* gm = (float*)ws + (size_t)B * lossdc::NBLK * (lossdc::ZMAX * lossdc::ZMAX + 1);
-  hipLaunchKernelGGL(loss_dc_gradm_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)ws, D, C, gm);
-  const dim3 grid((unsigned)ceil_div(F, 8), (unsigned)ceil_div(B * T, 32));
-  hipLaunchKernelGGL(dc_head_grad_images_kernel, grid, dim3(256), 0, st, emb, inv_norm, one_hot, mag, (const float*)gm, g_per_utt, B, T,
-                     F, C, eps, img_rows, img_t, colsum);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-int onssen_loss_dc_grad_f32(const float* emb, const float* one_hot, const float* mag, int B, int TF, int D, int C,
-                            const float* g_per_utt, float* d_emb, void* ws, size_t ws_bytes, void* stream) {
-  if (!emb || !one_hot || !mag || !g_per_utt || !d_emb || !ws || B <= 0 || TF <= 0 || D <= 0 || C <= 0 || C > 4 ||
-      D + C > lossdc::ZMAX)
-    return ONSSEN_E_ARG;
-  if (ws_bytes < onssen_loss_dc_workspace_bytes(B)) return ONSSEN_E_WORKSPACE;
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  float* gm = (float*)ws + (size_t)B * lossdc::NBLK * (lossdc::ZMAX * lossdc::ZMAX + 1);
-  hipLaunchKernelGGL(loss_dc_gradm_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)ws, D, C, gm);
-  const int nb = ceil_div(TF, 256) > 64 ? 64 : ceil_div(TF, 256);
-  const dim3 grid((unsigned)nb, (unsigned)B);
-  if (D == 20 && aligned16(emb) && aligned16(d_emb))
-    hipLaunchKernelGGL((loss_dc_grad_kernel<20>), grid, dim3(256), 0, st, emb, one_hot, mag, gm, g_per_utt, TF, D, C, d_emb);
-  else
-    hipLaunchKernelGGL((loss_dc_grad_kernel<0>), grid, dim3(256), 0, st, emb, one_hot, mag, gm, g_per_utt, TF, D, C, d_emb);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-size_t onssen_batch_sdr_workspace_bytes(int B) {
-  return B > 0 ? ((size_t)B * sdr::NBLK * sdr::PSTRIDE + (size_t)B * sdr::SMAX) * sizeof(double) : 0;
-}
-
-static int batch_sdr_impl(const float* est, const float* org, const float* mask, int B, int C, int n, float* sdr_out,
-                          int* perm_out, void* ws, size_t ws_bytes, void* stream, const int32_t* lengths) {
-  if (!est || !org || !sdr_out || !ws || B <= 0 || C <= 0 || C > sdr::CMAX || n <= C) return ONSSEN_E_ARG;
-  if (ws_bytes < onssen_batch_sdr_workspace_bytes(B)) return ONSSEN_E_WORKSPACE;
-  ONSSEN_CLEAR_ERROR();
-  hipStream_t st = (hipStream_t)stream;
-  if ((reinterpret_cast<uintptr_t>(ws) & 7u) != 0) return ONSSEN_E_ALIGN;
-  double* partial = (double*)ws;      // fp64 sums: see loss_sdr.inc
-  double* means = partial + (size_t)B * sdr::NBLK * sdr::PSTRIDE;
-  const dim3 grid(sdr::NBLK, (unsigned)B);
-  hipLaunchKernelGGL((sdr_partial_kernel<0>), grid, dim3(256), 0, st, est, org, mask, C, n, (const double*)nullptr, partial, lengths);
-  hipLaunchKernelGGL(sdr_means_kernel, dim3((unsigned)B), dim3(64), 0, st, (const double*)partial, C, n, means, lengths);
-  hipLaunchKernelGGL((sdr_partial_kernel<1>), grid, dim3(256), 0, st, est, org, mask, C, n, (const double*)means, partial, lengths);
-  hipLaunchKernelGGL(sdr_final_kernel, dim3((unsigned)B), dim3(64), 0, st, (const double*)partial, C, sdr_out, perm_out);
-  ONSSEN_LAUNCH_CHECK();
-  return ONSSEN_OK;
-}
-
-
-int onssen_batch_sdr_f32(const float* est, const float* org, const float* mask, int B, int C, int n, float* sdr_out,
-                         int* perm_out, void* ws, size_t ws_bytes, void* stream) {
-  return batch_sdr_impl(est, org, mask, B, C, n, sdr_out, perm_out, ws, ws_bytes, stream, nullptr);
-}
-
-int onssen_batch_sdr_ragged_f32(const float* est, const float* org, const float* mask, int B, int C, int n,
-                                const int32_t* lengths, float* sdr_out, int* perm_out, void* ws, size_t ws_bytes,
-                                void* stream) {
-  if (!lengths) return ONSSEN_E_ARG;
-  return batch_sdr_impl(est, org, mask, B, C, n, sdr_out, perm_out, ws, ws_bytes, stream, lengths);
 }
 
 // ---- training: weight images for the backward recurrence (the training forward and the backward itself: lstm_run.inc) ----

@@ -179,17 +179,6 @@ static Ws ws_layout(const Cfg& g, int n, int S) {
   return ws_layout_rows(g, (size_t)f.M, (size_t)n * ceil_div(f.T, ROWS_PER_CHUNK));
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
 // ---- packing ----------------------------------------------------------------------------------------------------------------
 // rows x K (row-major, contiguous) -> rows x ld (zeros in columns [K, ld))
 __global__ __launch_bounds__(256) void tas_copy_pad_kernel(const float* __restrict__ src, long rows, int K, int ld,
