@@ -770,6 +770,29 @@ int onssen_mag_istft_ragged_f32(const float* stft_ri, const float* mag, int64_t 
 int onssen_istft_backward_f32(const float* stft_ri, const float* operand, int64_t m_sb, int64_t m_sc, int64_t m_st, int64_t m_sf,
                               const float* phase, int64_t p_sc, int mode, int B, int C, int T, const int32_t* frames, int n_fft, int hop,
                               int length, const int32_t* lengths, const float* g_out, float* g_operand, float* g_phase, void* stream);
+/* onssen_misi_phase_backward_f32: the adjoint of onssen_misi_phase_f32 / onssen_misi_phase_ragged_f32 (csrc/misi_bwd.inc) -- with
+ * onssen_istft_backward_f32 in mode 1, which returns the gradient at the phase maps, what training through K unfolded MISI
+ * iterations needs.  mix, est and their strides as in the forward; n_per_utt NULL: a uniform batch.  g_phase (C, B, T, F, 2)
+ * CONTIGUOUS float32, T = 1 + n_max/hop: the gradient at the forward's `phase`; g_est (B, C, n_max) CONTIGUOUS float32: the
+ * gradient at `est` (the mixture is data and gets none).  With Z_c the forward's spectra, recomputed in fp64 from the same
+ * float32 mix and est (the forward's float32 `phase` is not an input), and p = Z / |Z|:
+ *   g_Z = (g_phase - p (p . g_phase)) / |Z|           0 wherever the forward wrote its (1, 0) fallback
+ *   r_t = w[i] * sum_f H[f] e^{+2 pi i f i / N}       H[f] = g_Z[f] / 2 for 0 < f < N/2, Re g_Z[f] at f in {0, N/2}, Hermitian beyond
+ *   g_u = overlap-add of r_t over the reflect-padded axis, the padding folded back about sample 0 and sample n_b - 1
+ *   g_est_c = g_u_c - (1 / C) sum_j g_u_j
+ * Two launches (transform per frame and speaker pair; gather per sample), fp64 throughout with one rounding on the store, sums
+ * in a fixed order, no atomics: bit-repeatable, nothing read back by the host, capturable in a graph.  Ragged: row b inside
+ * n_per_utt[b] is bit for bit the batch-1 call on that row, exactly 0 after it; nothing of mix / est beyond n_per_utt[b] and
+ * nothing of g_phase at frames >= 1 + n_per_utt[b]/hop is read; a device length is kept inside (n_fft/2, n_max].
+ * ws: caller-owned, 8-byte aligned, onssen_misi_phase_backward_workspace_bytes(B, C, n_max, n_fft, hop) bytes (0 for a refused
+ * geometry), needs no zeroing.
+ * Refused before anything is launched or written: a NULL pointer (n_per_utt may be NULL), B < 1, C < 2, C > 8, hop < 1,
+ * hop > n_fft, n_max <= n_fft/2, n_fft not in {256, 512, 1024} (ONSSEN_E_ARG); a short ws (ONSSEN_E_WORKSPACE); g_phase or ws
+ * off an 8-byte boundary (ONSSEN_E_ALIGN). */
+size_t onssen_misi_phase_backward_workspace_bytes(int B, int C, int n, int n_fft, int hop);
+int onssen_misi_phase_backward_f32(const float* mix, int64_t mix_stride, const float* est, int64_t est_sb, int64_t est_sc, int B,
+                                   int C, int n_max, const int32_t* n_per_utt, int n_fft, int hop, const float* g_phase,
+                                   float* g_est, void* ws, size_t ws_bytes, void* stream);
 /* The waveform L1 loss with the best permutation.  est (B, C, n) contiguous (the inverse transform's output); ref (b, j) at
  * ref + b*r_sb + j*r_sc, unit sample stride, |stride| >= n; C <= 4.  Per row with n_b = lengths[b] valid samples (NULL: n; a device
  * value is clamped to [1, n]):

@@ -141,6 +141,9 @@ SIGNATURES = {
     "onssen_mag_istft_ragged_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     # waveform-approximation training: the adjoint of the three inverse transforms, the L1 PIT waveform loss and its gradient
     "onssen_istft_backward_f32": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    # unfolded MISI training: the adjoint of onssen_misi_phase(_ragged)_f32
+    "onssen_misi_phase_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "onssen_misi_phase_backward_f32": (_i, [_vp, _i64, _vp, _i64, _i64, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "onssen_wa_pit_workspace_bytes": (_sz, [_i, _i]),
     "onssen_wa_pit_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "onssen_wa_pit_backward_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -676,6 +679,18 @@ class Lib:
         self.check(self.dll.onssen_istft_backward_f32(stft_ri, operand, m_sb, m_sc, m_st, m_sf, phase, p_sc, mode, B, Cn, T, frames,
                                                       n_fft, hop, length, lengths, g_out, g_operand, g_phase, stream),
                    "onssen_istft_backward_f32")
+
+    def misi_phase_backward_workspace_bytes(self, B, Cn, n, n_fft, hop):
+        nb = int(self.dll.onssen_misi_phase_backward_workspace_bytes(B, Cn, n, n_fft, hop))
+        if nb == 0:
+            self.check(-1, "onssen_misi_phase_backward_workspace_bytes")
+        return nb
+
+    def misi_phase_backward(self, mix, mix_stride, est, est_sb, est_sc, B, Cn, n, n_fft, hop, g_phase, g_est, ws, ws_bytes, stream,
+                            n_per_utt=None):
+        """The adjoint of misi_phase: g_phase (C, B, T, F, 2) -> g_est (B, C, n), both contiguous; n_per_utt as in the forward."""
+        self.check(self.dll.onssen_misi_phase_backward_f32(mix, mix_stride, est, est_sb, est_sc, B, Cn, n, n_per_utt, n_fft, hop, g_phase,
+                                                           g_est, ws, ws_bytes, stream), "onssen_misi_phase_backward_f32")
 
     # ---- waveform-approximation loss: L1 distance with the best permutation ---
     def wa_pit_workspace_bytes(self, B, Cn):

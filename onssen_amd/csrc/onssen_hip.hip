@@ -9,6 +9,9 @@
 //                       STFT of two speakers per transform, Z / |Z|: the phase maps of the next onssen_phase_istft_f32)
 //   istft_bwd.inc       istft_bwd_kernel (waveform-approximation training: the adjoint of mask_istft_kernel in its three modes -- windowed
 //                       fp64 forward transform of the waveform gradient, two speakers per transform, gradients of masks / phases / magnitudes)
+//   misi_bwd.inc        misi_bwd_frames_kernel / misi_bwd_gather_kernel (unfolded MISI training: the adjoint of misi_phase_kernel -- forward
+//                       transform, Z / |Z| Jacobian and inverse transform per frame in one LDS buffer, then the overlap-add with the
+//                       reflect padding folded back and the residual adjoint)
 //   gemm.inc            linear_x3q_kernel (K3/K7/K8/K9 on pre-split bf16 images: 256|128 x 320|256 tiles staged by LDS-DMA into a swizzled
 //                       layout, 8 waves, register epilogues), linear_x3p_kernel (round-1 form: 256x160 tiles; batched weight gradients;
 //                       bias | sigmoid | grouped L2-norm), linear_x3_kernel / linear_kernel (fp32-A forms, exact-fp32 MFMA),
@@ -151,6 +154,7 @@ static unsigned& xcd_spin_limit() {
 #include "fft.inc"
 #include "misi.inc"       // MISI phase reconstruction: the half-step between two inverse transforms (estimates -> phase maps)
 #include "istft_bwd.inc"  // waveform-approximation training: the adjoint of mask_istft_kernel, all three modes
+#include "misi_bwd.inc"   // unfolded MISI training: the adjoint of misi_phase_kernel (phase-map gradients -> estimate gradients)
 #include "pit.inc"        // permutation-invariant losses: the shared geometry, loads, permutation enumerator, sums and host helpers
 #include "loss_dc.inc"    // deep-clustering loss and its gradient: its kernels and its C ABI entries
 #include "batch_sdr.inc"  // batch SI-SDR with best permutation: its kernels and its C ABI entries

@@ -281,6 +281,43 @@ def phase_istft(stft_ri, masks, phases, hop_size=64, length=None, frames=None, l
     return out
 
 
+class _MisiPhaseGrad(torch.autograd.Function):
+    """misi_phase with its backward on the device.  The forward is the plain call on the detached inputs (the same launch, the
+    same bits); the backward is ``onssen_misi_phase_backward_f32`` (csrc/misi_bwd.inc): two launches from the gradient at the
+    (C,B,T,F,2) phase maps to the gradient at the (B,C,n) estimates, the Jacobian at the float32 estimates evaluated in fp64.
+    The mixture is data and gets no gradient; the workspace is allocated per backward call (the caching allocator: no
+    synchronisation, capturable)."""
+
+    @staticmethod
+    def forward(ctx, window_size, hop, lengths, mix, est):
+        mix, est = mix.detach(), est.detach()
+        out = misi_phase(mix, est, window_size, hop, lengths)
+        ctx.saved = (mix, est, lengths)
+        ctx.geom = (window_size, hop)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        window_size, hop = ctx.geom
+        mix, est, lengths = ctx.saved
+        mix, est = mix.float(), est.float()
+        if mix.stride(1) != 1:
+            mix = mix.contiguous()
+        if est.stride(2) != 1:
+            est = est.contiguous()
+        B, C, n = est.shape
+        g = g.float().contiguous()
+        lib = get_lib()
+        nbytes = lib.misi_phase_backward_workspace_bytes(B, C, n, window_size, hop)
+        ws = torch.empty(nbytes // 8, device=g.device, dtype=torch.float64)
+        g_est = torch.empty(B, C, n, device=g.device, dtype=torch.float32)
+        lib.misi_phase_backward(mix.data_ptr(), mix.stride(0), est.data_ptr(), est.stride(0), est.stride(1), B, C, n, window_size, hop,
+                                g.data_ptr(), g_est.data_ptr(), ws.data_ptr(), nbytes, _stream(),
+                                n_per_utt=lengths.data_ptr() if lengths is not None else None)
+        return None, None, None, None, g_est
+
+
 def misi_phase(mix, est, window_size=256, hop_size=64, lengths=None, out=None):
     """The half-step of MISI (multiple input spectrogram inversion) between two inverse transforms, one launch (csrc/misi.inc):
     mix (B, n), est (B, C, n) float32 cuda tensors, 2 <= C <= 8 -> (C, B, T, F, 2) float32 unit phase vectors, T = 1 + n // hop,
@@ -290,11 +327,26 @@ def misi_phase(mix, est, window_size=256, hop_size=64, lengths=None, out=None):
 
     ``lengths`` (B,): a RAGGED batch as in ``stft_logmag`` -- nothing beyond lengths[b] is read, row b's own 1 + lengths[b] // hop
     frames are bit for bit those of a batch-1 call, the frames after them are silence, (1, 0).  ``out``: a (C, B, T, F, 2) float32
-    contiguous tensor to write into instead of a new one."""
+    contiguous tensor to write into instead of a new one.
+
+    Differentiable with respect to ``est``: when autograd is on and it requires a gradient, the same launch runs inside an autograd
+    node whose backward is ``onssen_misi_phase_backward_f32`` (csrc/misi_bwd.inc) -- what training through unfolded MISI
+    iterations needs (``separation.misi``, ``loss.loss_wa_misi``); ``out=`` together with such an input raises, and so does a
+    ``mix`` that requires a gradient: the mixture is data."""
+    if _wants_grad(mix):
+        raise RuntimeError("misi_phase: mix requires a gradient; the mixture is data -- the backward gives the gradient of the estimates only")
+    if _wants_grad(est) and out is not None:
+        raise ValueError("misi_phase: out= cannot be combined with inputs that require a gradient")
     if not mix.is_cuda or not est.is_cuda:
         raise RuntimeError("misi_phase: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
     if mix.dim() != 2 or est.dim() != 3 or est.shape[0] != mix.shape[0] or est.shape[2] != mix.shape[1]:
         raise ValueError(f"misi_phase: expected mix (B, n) and est (B, C, n), got {tuple(mix.shape)} and {tuple(est.shape)}")
+    if _wants_grad(est):
+        if not 2 <= est.shape[1] <= 8:
+            raise ValueError(f"misi_phase: {est.shape[1]} speakers; the kernel takes 2 .. 8")
+        if lengths is not None:
+            lengths = _lengths_i32(lengths, est.shape[0], est.shape[2], mix.device, "lengths", lo=window_size // 2 + 1)
+        return _MisiPhaseGrad.apply(window_size, hop_size, lengths, mix, est.float())
     mix, est = mix.float(), est.float()
     if mix.stride(1) != 1:
         mix = mix.contiguous()

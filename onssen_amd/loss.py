@@ -931,34 +931,15 @@ def loss_wa(output, label, hop_size=64, frames=None, lengths=None, kind="chimera
       "phase"    [embedding, mask_A, mask_B, phase_A, phase_B] of the phase network, through ``phase_istft``
       "enhance"  [magnitude] of the enhancement network, through ``mag_istft``: one channel, the identity assignment
     ``frames`` / ``lengths`` (B,): a ragged batch as in ``mask_istft`` (both or neither); ``lengths`` also bounds the loss's sums.
-    ``misi_iters``: unfolded MISI iterations as training layers need the adjoint of ``misi_phase``; anything but 0 raises
-    NotImplementedError.  The mixture's spectrum is data: a ``stft_ri`` that requires a gradient raises."""
+    ``misi_iters``: this loss is the single inverse transform; anything but 0 raises NotImplementedError -- unfolded MISI
+    iterations as training layers (the adjoint of misi_phase) are ``loss_wa_misi``.  The mixture's spectrum is data: a
+    ``stft_ri`` that requires a gradient raises."""
     from . import features
     if misi_iters != 0:
-        raise NotImplementedError(f"loss_wa: misi_iters = {misi_iters!r}; training through unfolded MISI iterations needs the adjoint of "
-                                  f"misi_phase (its reflect padding and the Z / |Z| Jacobian), which is not built -- only misi_iters = 0 is")
-    if kind not in WA_KINDS:
-        raise ValueError(f"loss_wa: unknown kind {kind!r}; one of {WA_KINDS}")
-    output = list(output)
-    want = {"chimera": (3,), "phase": (5,), "enhance": (1,), "upit": (2, 3, 4)}[kind]
-    if len(output) not in want:
-        raise ValueError(f"loss_wa: {len(output)} output tensors for kind {kind!r}, which has {' or '.join(map(str, want))}")
-    if len(label) != 2:
-        raise ValueError(f"loss_wa: {len(label)} label tensors; the label is [stft_ri_mix (B,T,F,2), sig_ref (B,C,n)]")
-    stft_ri, sig_ref = label
-    if stft_ri.dim() != 4 or stft_ri.shape[-1] != 2 or sig_ref.dim() != 3:
-        raise ValueError(f"loss_wa: expected stft_ri_mix (B,T,F,2) and sig_ref (B,C,n), got {tuple(stft_ri.shape)} and {tuple(sig_ref.shape)}")
-    if stft_ri.requires_grad:
-        raise RuntimeError("loss_wa: stft_ri_mix requires a gradient; the mixture's spectrum is data")
-    masks = output[1:3] if kind in ("chimera", "phase") else output
-    B, T, F = stft_ri.shape[:3]
-    for m in masks:
-        if tuple(m.shape) != (B, T, F):
-            raise ValueError(f"loss_wa: an output of shape {tuple(m.shape)} for a spectrum of {(B, T, F)} bins")
-    if tuple(sig_ref.shape[:2]) != (B, len(masks)):
-        raise ValueError(f"loss_wa: sig_ref {tuple(sig_ref.shape)} for a batch of {B} with {len(masks)} estimates")
-    if (frames is None) != (lengths is None):
-        raise ValueError("loss_wa: a ragged batch needs both frames= and lengths=")
+        raise NotImplementedError(f"loss_wa: misi_iters = {misi_iters!r}; this loss goes through ONE inverse transform and has no use for "
+                                  f"the adjoint of misi_phase -- training through unfolded MISI iterations is loss_wa_misi(output, label, "
+                                  f"iters, ...)")
+    stft_ri, sig_ref, masks, phases = _wa_args("loss_wa", output, label, frames, lengths, kind)
     n = sig_ref.shape[2]
     rag = dict(frames=frames, lengths=lengths)
     if kind == "enhance":
@@ -966,10 +947,67 @@ def loss_wa(output, label, hop_size=64, frames=None, lengths=None, kind="chimera
     else:
         base = _planes_base(masks)               # the network's own interleaved buffer when the masks are its planes
         if kind == "phase":
-            for p in output[3:]:
-                if tuple(p.shape) != (B, T, F, 2):
-                    raise ValueError(f"loss_wa: a phase map of shape {tuple(p.shape)}, expected {(B, T, F, 2)}")
-            est = features.phase_istft(stft_ri, base, output[3:], hop_size, n, **rag)
+            est = features.phase_istft(stft_ri, base, phases, hop_size, n, **rag)
         else:
             est = features.mask_istft(stft_ri, base, hop_size, n, **rag)
+    return wa_pit(est, sig_ref, lengths).mean()
+
+
+def _wa_args(who, output, label, frames, lengths, kind):
+    """The argument checks of the waveform-approximation losses -> (stft_ri, sig_ref, masks, phase maps or None)."""
+    if kind not in WA_KINDS:
+        raise ValueError(f"{who}: unknown kind {kind!r}; one of {WA_KINDS}")
+    output = list(output)
+    want = {"chimera": (3,), "phase": (5,), "enhance": (1,), "upit": (2, 3, 4)}[kind]
+    if len(output) not in want:
+        raise ValueError(f"{who}: {len(output)} output tensors for kind {kind!r}, which has {' or '.join(map(str, want))}")
+    if len(label) != 2:
+        raise ValueError(f"{who}: {len(label)} label tensors; the label is [stft_ri_mix (B,T,F,2), sig_ref (B,C,n)]")
+    stft_ri, sig_ref = label
+    if stft_ri.dim() != 4 or stft_ri.shape[-1] != 2 or sig_ref.dim() != 3:
+        raise ValueError(f"{who}: expected stft_ri_mix (B,T,F,2) and sig_ref (B,C,n), got {tuple(stft_ri.shape)} and {tuple(sig_ref.shape)}")
+    if stft_ri.requires_grad:
+        raise RuntimeError(f"{who}: stft_ri_mix requires a gradient; the mixture's spectrum is data")
+    masks = output[1:3] if kind in ("chimera", "phase") else output
+    B, T, F = stft_ri.shape[:3]
+    for m in masks:
+        if tuple(m.shape) != (B, T, F):
+            raise ValueError(f"{who}: an output of shape {tuple(m.shape)} for a spectrum of {(B, T, F)} bins")
+    if tuple(sig_ref.shape[:2]) != (B, len(masks)):
+        raise ValueError(f"{who}: sig_ref {tuple(sig_ref.shape)} for a batch of {B} with {len(masks)} estimates")
+    if (frames is None) != (lengths is None):
+        raise ValueError(f"{who}: a ragged batch needs both frames= and lengths=")
+    phases = None
+    if kind == "phase":
+        phases = output[3:]
+        for p in phases:
+            if tuple(p.shape) != (B, T, F, 2):
+                raise ValueError(f"{who}: a phase map of shape {tuple(p.shape)}, expected {(B, T, F, 2)}")
+    return stft_ri, sig_ref, masks, phases
+
+
+def loss_wa_misi(output, label, iters, hop_size=64, frames=None, lengths=None, kind="chimera"):
+    """``loss_wa`` through ``iters`` unfolded MISI iterations (Wang, Le Roux, Wang & Hershey 2018: the phase reconstruction as
+    training layers): the network's masks go through the inverse transform, then ``iters`` times through ``features.misi_phase``
+    and ``features.phase_istft`` (``separation.misi`` with autograd on: every launch a node, the half-step's backward
+    csrc/misi_bwd.inc), and the final estimates are compared with the source waveforms, ``wa_pit(...).mean()``.
+
+    ``output``, ``label`` = [stft_ri_mix (B,T,F,2), sig_ref (B,C,n)], ``frames`` / ``lengths`` and the kinds "chimera", "upit" and
+    "phase" (whose network phases start the iterations) as in ``loss_wa``; "enhance" raises: with one source there is no
+    residual to redistribute.  The mixture waveform MISI needs is the inverse transform of ``stft_ri_mix``
+    (``mask_istft(stft_ri, None, ...)``, as the testers take it), so the "chimera-wa" / "upit-wa" loaders serve as they are; it
+    and the spectrum are data.  ``iters`` = 0 is exactly ``loss_wa``: the same launches, value and gradients."""
+    from . import features
+    from .separation import _misi_iters, misi
+    iters = _misi_iters(iters, "loss_wa_misi")
+    if kind == "enhance":
+        raise ValueError("loss_wa_misi: kind 'enhance' has one source: MISI spreads the mixture's residual over several, there is "
+                         "nothing to redistribute -- use loss_wa")
+    stft_ri, sig_ref, masks, phases = _wa_args("loss_wa_misi", output, label, frames, lengths, kind)
+    if iters == 0:
+        return loss_wa(output, label, hop_size, frames, lengths, kind)
+    n = sig_ref.shape[2]
+    with torch.no_grad():
+        wav = features.mask_istft(stft_ri, None, hop_size, n, frames=frames, lengths=lengths)[:, 0]
+    est = misi(stft_ri, _planes_base(masks), wav, iters, hop_size, frames=frames, lengths=lengths, phases=phases)
     return wa_pit(est, sig_ref, lengths).mean()

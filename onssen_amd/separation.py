@@ -28,7 +28,6 @@ def _misi_iters(iters, who):
     return int(iters)
 
 
-@torch.no_grad()
 def misi(stft_ri, masks, wav, iters, hop_size=64, frames=None, lengths=None, phases=None):
     """MISI (multiple input spectrogram inversion: Gunawan & Sen 2010; the phase reconstruction of Wang, Le Roux, Wang & Hershey
     2018 after a chimera++ network) on the device: stft_ri (B,T,F,2) the mixture's spectrum, masks (B,T,F,C) (any strides), wav
@@ -39,8 +38,13 @@ def misi(stft_ri, masks, wav, iters, hop_size=64, frames=None, lengths=None, pha
 
     ``iters`` = 0 returns exactly ``mask_istft(...)`` (``phase_istft(...)`` with ``phases``) and launches nothing else.  ``frames``
     / ``lengths`` (B,): a ragged batch as in ``mask_istft`` (both or neither).  Nothing is read back by the host and the
-    phase buffer and the estimates are allocated once per call, so a call can be captured in a hipGraph."""
-    from .features import misi_phase, phase_istft
+    phase buffer and the estimates are allocated once per call, so a call can be captured in a hipGraph.
+
+    Unfolded MISI as training layers (Wang et al. 2018): when autograd is on and ``masks`` or ``phases`` require a gradient, the
+    same launches run as a chain of autograd nodes (``mask_istft`` / ``phase_istft`` -> ``misi_phase`` -> ``phase_istft`` -> ...)
+    with fresh buffers per iteration, and the result is differentiable with respect to them; the mixture (``stft_ri``, ``wav``)
+    is data.  Otherwise nothing is recorded and the buffers are re-used as above."""
+    from .features import _wants_grad
     iters = _misi_iters(iters, "misi")
     if (frames is None) != (lengths is None):
         raise ValueError("misi: a ragged batch needs both frames= and lengths=")
@@ -48,6 +52,14 @@ def misi(stft_ri, masks, wav, iters, hop_size=64, frames=None, lengths=None, pha
         raise RuntimeError("misi: needs tensors on a ROCm device; onssen_amd has no CPU fallback")
     if wav.dim() == 1:
         wav = wav[None]
+    track = _wants_grad(masks, *(() if phases is None else [phases] if torch.is_tensor(phases) else phases))
+    with torch.enable_grad() if track else torch.no_grad():
+        return _misi(stft_ri, masks, wav, iters, hop_size, frames, lengths, phases, track)
+
+
+def _misi(stft_ri, masks, wav, iters, hop_size, frames, lengths, phases, track):
+    """``misi`` after its checks; ``track``: every launch is an autograd node with buffers of its own."""
+    from .features import misi_phase, phase_istft
     n = wav.shape[-1]
     if phases is not None:
         est = phase_istft(stft_ri, masks, phases, hop_size, n, frames=frames, lengths=lengths)
@@ -63,8 +75,8 @@ def misi(stft_ri, masks, wav, iters, hop_size=64, frames=None, lengths=None, pha
     n_fft = 2 * (stft_ri.shape[2] - 1)
     ph = None
     for _ in range(iters):
-        ph = misi_phase(wav, est, n_fft, hop_size, lengths=lengths, out=ph)
-        est = phase_istft(stft_ri, masks, ph, hop_size, n, frames=frames, lengths=lengths, out=est)
+        ph = misi_phase(wav, est, n_fft, hop_size, lengths=lengths, out=None if track else ph)
+        est = phase_istft(stft_ri, masks, ph, hop_size, n, frames=frames, lengths=lengths, out=None if track else est)
     return est
 
 
